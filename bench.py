@@ -22,6 +22,14 @@ Workload (config C3, BASELINE.json configs[2]): 4096 two-ship AST envs per GPU, 
 with PTI machinery, HeadingBySampledRouteController, reward_designs, collav = sbmpc (the runner
 default, run/ast-sac_runner.py:35), dt = 4 s. Weak scaling: envs per GPU fixed.
 
+A plain run does only what the headline needs: set-up, `--warmup` launches, the `--steps` timed launches, the
+result line (`ms_per_step`: wall milliseconds per timed launch). `--full` adds every secondary leg after the
+headline (the same stream without the launch tail, C2, the policy stream, SAC, C4, C5, the CPU baseline); their
+fields of the line are null without it. `--dump-outputs DIR` writes the decision records the timed stream
+computed as DIR/decision_records.npy, [env, table episode, decision, record column] float64, with
+DIR/env_index.npy naming the envs (all of them up to 64 MB, else a fixed seeded sample). The table and every
+env's start are seeded, so the records of two runs, or two builds, compare element by element.
+
 Launch:  python bench.py                       (N = 1)
          python bench.py --gpus N              (spawns N ranks itself: a child torch.distributed.run;
                                                 this parent process never touches the GPU)
@@ -85,7 +93,37 @@ def parse():
     p.add_argument("--c4-envs", type=int, default=8192, help="C4 leg: envs per rank (C4: 65,536 over 8 GPUs)")
     p.add_argument("--c4-loops", type=int, default=3, help="C4 leg: timed train loops")
     p.add_argument("--no-c5", action="store_true", help="skip the C5 legs (K = 2 and 4 obstacle ships, sbmpc)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every secondary leg (the stream without the launch tail, C2, "
+                        "policy stream, SAC, C4, C5, CPU baseline; each with its own --no-* switch); without it "
+                        "only the headline stream runs and those fields of the result line are null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed stream computed to DIR/<name>.npy (float64; see dump_outputs)")
     return p.parse_args()
+
+
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_sample(n_envs, bytes_per_env, rank):
+    """The envs whose outputs are written: all of them while that stays under DUMP_MAX_BYTES, else a fixed
+    seeded sample (sorted) of as many as fit."""
+    import numpy as np
+    fit = int(DUMP_MAX_BYTES // bytes_per_env)
+    if n_envs <= fit:
+        return np.arange(n_envs)
+    return np.sort(np.random.Generator(np.random.PCG64(20251019 + rank)).choice(n_envs, fit, replace=False))
+
+
+def dump_outputs(path, rank, arrays):
+    """--dump-outputs: one float64 .npy per array (rank > 0 writes <name>.rank<r>.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if not np.isfinite(a).all():
+            raise SystemExit(f"bench.py: output {name} holds {int((~np.isfinite(a)).sum())} non-finite values")
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
 
 
 def host_threads():
@@ -619,12 +657,12 @@ def main():
     ep_idx = torch.zeros(N, dtype=torch.long, device=dev)
     dec_idx = torch.zeros(N, dtype=torch.long, device=dev)
     ar = torch.arange(N, device=dev)
-    out = dict(obs=torch.empty((N, 8), dtype=torch.float32, device=dev),
-               reward=torch.empty(N, dtype=torch.float64, device=dev),
-               done=torch.empty(N, dtype=torch.uint8, device=dev),
-               events=torch.empty(N, dtype=torch.int32, device=dev),
-               ticks=torch.empty(N, dtype=torch.int32, device=dev),
-               ready=torch.empty(N, dtype=torch.uint8, device=dev))
+    out = dict(obs=torch.zeros((N, 8), dtype=torch.float32, device=dev),  # (zeros: --dump-outputs writes them)
+               reward=torch.zeros(N, dtype=torch.float64, device=dev),
+               done=torch.zeros(N, dtype=torch.uint8, device=dev),
+               events=torch.zeros(N, dtype=torch.int32, device=dev),
+               ticks=torch.zeros(N, dtype=torch.int32, device=dev),
+               ready=torch.zeros(N, dtype=torch.uint8, device=dev))
     obs_reset = torch.empty((N, 8), dtype=torch.float32, device=dev)
     total_ticks = torch.zeros((), dtype=torch.int64, device=dev)
     total_decisions = torch.zeros((), dtype=torch.int64, device=dev)
@@ -647,6 +685,23 @@ def main():
     dlog = torch.zeros((N, dlog_cap, abi.DECLOG_COLS), dtype=torch.float64, device=dev)
     dlog_len = torch.zeros(N, dtype=torch.int32, device=dev)
     dlog_max = torch.zeros((), dtype=torch.int32, device=dev)
+    # --dump-outputs, table mode: the decision records by (env, table episode, decision). The launch tail makes
+    # the tick at which a launch leaves an env depend on timing, so which decisions fall into the last launch
+    # differs from run to run; the record of a given (env, table episode, decision) does not (an env's stream
+    # repeats every `table_eps` episodes). Every launch's records are therefore filed under that key, the last
+    # launch's last. A key never reached (the episode ended before that decision, or the run was too short) keeps
+    # an all-zero record, which no decision writes (its tick count is at least 1). (One more slot per env takes
+    # the ring's unused rows.)
+    n_keys = table_eps * n_dec
+    records = None
+    if args.dump_outputs and args.mode == "table":
+        records = torch.zeros((N, n_keys + 1, abi.DECLOG_COLS), dtype=torch.float64, device=dev)
+        dlog_slot = torch.arange(dlog_cap, device=dev)[None, :]
+
+    def file_records():
+        key = (dlog[:, :, abi.DL_EPISODE].long() % table_eps) * n_dec + dlog[:, :, abi.DL_DECISION].long()
+        key = torch.where(dlog_slot < dlog_len[:, None], key.clamp_(0, n_keys - 1), n_keys)
+        records[ar[:, None].expand_as(key), key] = dlog
 
     def one_step_table(timed_i=None):
         dlog_len.zero_()
@@ -656,6 +711,8 @@ def main():
         torch.maximum(dlog_max, dlog_len.max(), out=dlog_max)
         if timed_i is not None:
             ev1[timed_i].record()
+        if records is not None:
+            file_records()
         total_ticks.add_(tout["ticks"].sum())
         total_decisions.add_(tout["decisions"].sum())
 
@@ -696,10 +753,26 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
 
+    if args.dump_outputs:
+        progress("writing outputs")
+        if args.mode == "table":
+            keep = dump_sample(N, (n_keys * abi.DECLOG_COLS + 3) * 8, rank)
+            rec = records[torch.from_numpy(keep).to(dev), :n_keys].cpu().numpy()
+            rec[:, :, abi.DL_EPISODE] %= table_eps  # the episode counter -> its table row
+            arrays = {"decision_records": rec.reshape(len(keep), table_eps, n_dec, abi.DECLOG_COLS)}
+            if args.tail_ticks <= 0:  # without the launch tail the last launch's per-env counts are fixed too
+                arrays.update({k: tout[k].cpu().numpy()[keep] for k in ("ticks", "decisions")})
+        else:  # what the last shipsim_step call returned
+            keep = dump_sample(N, (8 + 5 + 1) * 8, rank)
+            arrays = {k: v.cpu().numpy()[keep] for k, v in out.items()}
+        arrays["env_index"] = keep
+        dump_outputs(args.dump_outputs, rank, arrays)
+        records = None
+
     # the same stream without the launch tail (the training collector's default, FUSED_TAIL = 0), beside the
     # headline, which runs with it (--tail-ticks): the same number of launches, continuing the same envs
     tail_off = None
-    if args.mode == "table" and args.tail_ticks > 0:
+    if args.full and args.mode == "table" and args.tail_ticks > 0:
         progress("headline stream without the launch tail")
         sim.set_stream_tail(0)
         off_ticks = torch.zeros((), dtype=torch.int64, device=dev)
@@ -773,19 +846,21 @@ def main():
                                  "instructions) per launch / this run's mean launch time: the FP64 VALU rate the "
                                  "kernel issues; 'distinct' counts each ship's chain once (its LPE/2 sub-lanes "
                                  "repeat it)"}
-    progress("c2 single ships")
-    c2 = bench_c2(dev) if (rank == 0 and not args.no_c2) else None
-    progress("policy stream")
+    if args.full:
+        progress("c2 single ships")
+    c2 = bench_c2(dev) if (args.full and rank == 0 and not args.no_c2) else None
+    if args.full:
+        progress("policy stream")
     pstream = (bench_policy_stream(dev, cfg, N, args.slice if args.mode == "table" else 4096,
                                    tail_ticks=max(args.tail_ticks, 0) if args.mode == "table" else 0)
-               if (rank == 0 and not args.no_policy_stream and args.obs_ships == 1) else None)
+               if (args.full and rank == 0 and not args.no_policy_stream and args.obs_ships == 1) else None)
     if pstream is not None:  # the runner's --layer_size 512: the in-kernel fc1 in two 256-unit slices
         p512 = bench_policy_stream(dev, cfg, N, args.slice if args.mode == "table" else 4096, launches=1,
                                    tail_ticks=max(args.tail_ticks, 0) if args.mode == "table" else 0, hidden=512)
         pstream["hidden_512"] = {k: p512[k] for k in ("env_ticks_per_s", "decisions_per_s", "kernel_ms", "launches")}
-    progress("sac")
     sac = sac_ar = None
-    if args.sac_steps > 0:
+    if args.full and args.sac_steps > 0:
+        progress("sac")
         if args.sac_global_batch % world:
             raise SystemExit(f"--sac-global-batch {args.sac_global_batch} is not a multiple of {world} ranks")
         pgw = dist.group.WORLD if world > 1 else None
@@ -794,17 +869,17 @@ def main():
             sac_ar = bench_sac(dev, world, pgw, args.sac_steps, args.sac_global_batch, eager_steps=0,
                                dp_mode="allreduce")
     c4 = None
-    if not args.no_c4:
+    if args.full and not args.no_c4:
         progress("c4 loop")
         c4 = bench_c4(dev, world, rank, dist.group.WORLD if world > 1 else None, n_envs=args.c4_envs,
                       loops=args.c4_loops)
     c5 = None
-    if not args.no_c5 and args.obs_ships == 1:
+    if args.full and not args.no_c5 and args.obs_ships == 1:
         progress("c5 multi-obstacle")
         c5 = {f"k{k}": bench_c5(dev, world, N, k, rank=rank, tail_ticks=max(args.tail_ticks, 0)) for k in (2, 4)}
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N = 1 figure
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N = 1 figure
             progress("cpu baseline")
             cpu = cpu_baseline(cfg, args.cpu_baseline_seconds, host_threads()[0], N)
         line = {

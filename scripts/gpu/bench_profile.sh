@@ -5,7 +5,7 @@
 . "$(dirname "$0")/common.sh"
 TAG=${1:-bench}; PMC=${2:-}
 export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --sac-steps 0 --no-c2 --no-policy-stream --no-c4 --no-c5"
+B="$R/bench.py --full --no-cpu-baseline --sac-steps 0 --no-c2 --no-policy-stream --no-c4 --no-c5"
 if [ -n "$PMC" ]; then
   cd /tmp
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch_$TAG" -o run -- python3 $B \
@@ -21,11 +21,11 @@ if [ -n "$PMC" ]; then
   python scripts/pmc_fp64.py "$O/pmc_fp64_$TAG" "$O/pmc_fp64_$TAG.json" sbmpc 4096 4096 > "$O/pmc_fp64_$TAG.out"
   hard $? fp64_json
 fi
-timeout -k 10 500 python bench.py > "$O/bench_$TAG.log" 2>&1; hard $? bench
+timeout -k 10 500 python bench.py --full >"$O/bench_$TAG.log" 2>&1; hard $? bench
 tail -1 "$O/bench_$TAG.log"
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$TAG" -o run -- python3 "$R/bench.py" \
-  > "$O/prof_$TAG.log" 2>&1; hard $? rocprof_stats
+  --full > "$O/prof_$TAG.log" 2>&1; hard $? rocprof_stats
 cd "$R"
 python scripts/trace_summary.py "$O/prof_$TAG" "$O/prof_$TAG.log" "$O/trace_vs_bench_$TAG.json"; hard $? trace_summary
 find "$O" -name "*kernel_trace.csv" -delete

@@ -3,7 +3,7 @@
 #   bash scripts/gpu/inventory_classes.sh TAG
 . "$(dirname "$0")/common.sh"
 TAG=${1:-icl}
-B="$R/bench.py --no-cpu-baseline --sac-steps 0 --no-c2 --no-policy-stream --no-c4 --no-c5 --steps 3"
+B="$R/bench.py --full --no-cpu-baseline --sac-steps 0 --no-c2 --no-policy-stream --no-c4 --no-c5 --steps 3"
 timeout -k 10 300 python $B > "$O/icl_bench_$TAG.json" 2> "$O/icl_bench_$TAG.err"; hard $? bench
 cd /tmp
 timeout -s KILL 150 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT \

@@ -7,7 +7,7 @@ timeout -k 10 300 python -u -m pytest -x -v --timeout 120 --timeout-method threa
   tests/test_gpu_run_policy.py tests/test_gpu_policy_act.py > "$O/pt_pytest_$TAG.txt" 2>&1
 soft_pytest $? pytest; tail -3 "$O/pt_pytest_$TAG.txt"
 p() { python -c "import json;d=json.loads(open('$1').read().strip().splitlines()[-1]);s=d['extra']['policy_stream'] if 'extra' in d else d['policy_stream'];print(round(s['env_ticks_per_s']/1e6,1),'M', round(s['kernel_ms'],2),'ms')"; }
-B="--collav sbmpc --no-cpu-baseline --sac-steps 0 --no-c2"
+B="--full --collav sbmpc --no-cpu-baseline --sac-steps 0 --no-c2"
 for i in 1 2; do
   timeout -k 10 200 python bench.py $B > "$O/pt_${TAG}_tail_$i.log" 2>&1; hard $? tail
   timeout -k 10 200 python bench.py $B --tail-ticks 0 > "$O/pt_${TAG}_notail_$i.log" 2>&1; hard $? notail

@@ -2,7 +2,7 @@
 . "$(dirname "$0")/common.sh"
 TAG=${1:-r6g}
 bash scripts/gpu/suite.sh $TAG || exit $?
-timeout -k 10 600 python bench.py > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"; hard $? bench
+timeout -k 10 600 python bench.py --full >"$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"; hard $? bench
 python -c "
 import json;d=json.loads(open('$O/bench_$TAG.json').read().strip().splitlines()[-1])
 print('value', round(d['value']/1e6,1), 'ms', round(d['ms_per_step'],2), 'sac us', round(d['sac']['ms_per_grad_step']*1e3,2))

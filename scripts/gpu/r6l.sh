@@ -1,7 +1,7 @@
 # Round-6 call l: the 2-rank gloo rehearsal of the bench line on one GPU (the C4 leg over two ranks), the C4 ratio loop.
 . "$(dirname "$0")/common.sh"
 TAG=${1:-r6l}
-timeout -k 10 600 python bench.py --gpus 2 --dist-backend gloo --no-cpu-baseline --no-c2 --no-policy-stream --no-c5 \
+timeout -k 10 600 python bench.py --full --gpus 2 --dist-backend gloo --no-cpu-baseline --no-c2 --no-policy-stream --no-c5 \
   --steps 2 --sac-steps 100 > "$O/bench_gloo2_$TAG.json" 2> "$O/bench_gloo2_$TAG.err"; hard $? gloo2
 python -c "
 import json;d=json.loads(open('$O/bench_gloo2_$TAG.json').read().strip().splitlines()[-1])

@@ -26,11 +26,11 @@ timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WA
   python3 "$R/scripts/prof_sac.py" --steps 200 --graph 1 > "$O/pmc_sac_sq_$TAG.log" 2>&1; hard $? sac_sq
 cd "$R"
 echo "== bench"; date +%T
-timeout -k 10 500 python bench.py > "$O/bench_$TAG.log" 2>&1; hard $? bench
+timeout -k 10 500 python bench.py --full >"$O/bench_$TAG.log" 2>&1; hard $? bench
 tail -1 "$O/bench_$TAG.log" | cut -c1-400
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$TAG" -o run -- python3 "$R/bench.py" \
-  > "$O/prof_$TAG.log" 2>&1; hard $? rocprof_stats
+  --full > "$O/prof_$TAG.log" 2>&1; hard $? rocprof_stats
 cd "$R"
 python scripts/trace_summary.py "$O/prof_$TAG" "$O/prof_$TAG.log" "$O/trace_vs_bench_$TAG.json"; hard $? trace_summary
 echo "== c4"; date +%T
@@ -39,7 +39,7 @@ tail -c 700 "$O/c4_loop_$TAG.json"; echo
 # the bench line's PMC inputs (HBM traffic, FP64 VALU), when the call has the time left for three short passes
 if [ "$SECONDS" -lt 780 ]; then
   echo "== pmc"; date +%T
-  B="$R/bench.py --no-cpu-baseline --sac-steps 0 --no-c2 --no-policy-stream --no-c4 --no-c5"
+  B="$R/bench.py --full --no-cpu-baseline --sac-steps 0 --no-c2 --no-policy-stream --no-c4 --no-c5"
   cd /tmp
   timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch_$TAG" -o run -- python3 $B \
     > "$O/pmc_fetch_$TAG.log" 2>&1; hard $? pmc_fetch

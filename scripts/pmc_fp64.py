@@ -30,7 +30,7 @@ def main(d, out, collav="sbmpc", envs="4096", slice_ticks="4096"):
                fp64_flops_per_launch=64.0 * avg["SQ_INSTS_VALU_FLOPS_FP64"],
                fp64_wave_instructions_per_launch=(avg["SQ_INSTS_VALU_FMA_F64"] + avg["SQ_INSTS_VALU_ADD_F64"]
                                                   + avg["SQ_INSTS_VALU_MUL_F64"] + avg["SQ_INSTS_VALU_TRANS_F64"]),
-               note="one rocprofv3 --pmc pass of python3 bench.py --no-cpu-baseline --sac-steps 0 --no-c2 "
+               note="one rocprofv3 --pmc pass of python3 bench.py --full --no-cpu-baseline --sac-steps 0 --no-c2 "
                     "(default steps/warmup), averaged over every ast_step_kernel dispatch; fp64_flops_per_launch = 64 lanes x "
                     "SQ_INSTS_VALU_FLOPS_FP64 (issued lane-FLOPs: exec-masked lanes included)")
     with open(out, "w") as f:

@@ -24,7 +24,7 @@ rows.sort()
 ms = [x[1] / 1e6 for x in rows]
 line = [ln for ln in open(bench_log) if ln.startswith("{")][-1]
 b = json.loads(line)
-res = dict(command="rocprofv3 --kernel-trace --stats -- python3 bench.py (default bench command)",
+res = dict(command="rocprofv3 --kernel-trace --stats -- python3 bench.py --full (the whole bench line)",
            ast_step_kernel_dispatches=len(ms), mean_ms_all=sum(ms) / max(1, len(ms)),
            mean_ms_timed_last=sum(ms[-b["steps"]:]) / max(1, len(ms[-b["steps"]:])),
            bench_kernel_ms_all_launches=b["roofline"].get("kernel_ms_all_launches"),
