@@ -134,15 +134,15 @@ class BatchedPathCollector:
 
     def _fused_supported(self):
         """The env library can run this collector's policy inside the env launch (shipsim_run_policy): a
-        device policy exposing its weights, one obstacle ship, obs dim 8, hidden a multiple of 64 up to 512, and the
-        wrapper's action bounds equal to the env's (so the in-kernel NormalizedBoxEnv mapping is the
-        wrapper's)."""
+        device policy exposing its weights, 1..MAX_OBS obstacle ships (the observation is 8 wide for every count),
+        obs dim 8, hidden a multiple of 64 up to 512, and the wrapper's action bounds equal to the env's (so the
+        in-kernel NormalizedBoxEnv mapping is the wrapper's)."""
         dp = self._device_policy
         if dp is None or not hasattr(dp, "weights"):
             return False
         base = self._base_env()
         sim = getattr(base, "sim", None)
-        if sim is None or sim.n_ships != 2 or not hasattr(sim, "run_policy"):
+        if sim is None or not 2 <= sim.n_ships <= 1 + abi.MAX_OBS or not hasattr(sim, "run_policy"):
             return False
         _, _, o, h = dp.weights()
         if o != 8 or h % 64 or not 64 <= h <= 512:

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include <new>
+#include <type_traits>
 
 #include "shipsim.h"
 #include "shipsim_device.hpp"
@@ -1111,11 +1112,12 @@ __device__ __forceinline__ DevState opaque(const DevState& S) {
 // The collector's policy inside the decision stream (shipsim_run_policy): TanhGaussianPolicy.forward
 // + TanhNormal.sample (gaussian_policy.py:105-118, distributions.py:394-425) or MakeDeterministic's
 // tanh(mean) (policies/base.py:54-64) on the observation of every env of the wave that needs its next
-// action, evaluated by the whole wave (wave-uniform control flow): up to 8 envs per pass share every
+// action, evaluated by the whole wave (wave-uniform control flow): up to kPolMaxRows envs per pass share every
 // weight load; lane l computes hidden units l, l + 64, ... (fmaf chains from the bias in input order,
 // h1 staged in LDS); the heads are reduced across the wave. fp32 as the policy.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPolMaxRows = 8;
+constexpr int kPolMultiRows = 4;  // the K > 1 kernels: 16 lanes per env, so a wave never holds more than 4 envs
 constexpr int kPolMaxHidden = 512;
 
 __device__ inline void philox_env(uint32_t c[4], uint32_t k0, uint32_t k1) {  // Philox4x32-10
@@ -1146,7 +1148,8 @@ __device__ __forceinline__ float wave_sum_f(float x) {  // butterfly: every lane
 // units [256c + l·nj, 256c + l·nj + nj), so one row of the transposed fc1 weight is one coalesced load per lane (a
 // float4 in a full slice) and the h1 rows in LDS are read as broadcast float4s; the fc1 accumulators of one slice
 // are live at a time (the register budget of H = 256 at every width), and each lane's head partials run on across
-// the slices in unit order.
+// the slices in unit order. ROWS: the envs served per pass (the acc / pm / ps registers and the rows of lds_h1).
+template <int ROWS>
 __device__ __forceinline__ float policy_actions(bool want, const float ns[8], int env, bool env_leader, int env_lane0,
                                                 int seq, const ChainArgs& CH, float* lds_h1) {
   SHIPSIM_LANE_CHECK(64, 5);
@@ -1166,11 +1169,11 @@ __device__ __forceinline__ float policy_actions(bool want, const float ns[8], in
   };
   constexpr int kJ = 4;  // units per lane per slice, at most
   while (req) {
-    // the next (up to) kPolMaxRows requesting envs: the lowest set bits of req (no indexed arrays: row e's
+    // the next (up to) ROWS requesting envs: the lowest set bits of req (no indexed arrays: row e's
     // source lane is recomputed from the mask, so nothing lands in scratch)
     const uint64_t rows = req;
     int E = 0;
-    for (uint64_t m = req; m && E < kPolMaxRows; m &= m - 1) ++E;
+    for (uint64_t m = req; m && E < ROWS; m &= m - 1) ++E;
     for (int e = 0; e < E; ++e) req &= req - 1;
     // fc0 + relu for every row, into LDS: unit u = b1[u] + sum_i W1[u][i] x[i], i ascending
     {
@@ -1199,19 +1202,19 @@ __device__ __forceinline__ float policy_actions(bool want, const float ns[8], in
     __syncthreads();  // (one wave per block)
     // per slice: fc1 + relu, acc[e][j] = b2[u] + sum_k W2[u][k] h1[e][k], k ascending (W2T row k is [H]
     // contiguous), folded into this lane's head partials pm / ps (fmaf chains over its units in order)
-    float pm[kPolMaxRows], ps[kPolMaxRows];
+    float pm[ROWS], ps[ROWS];
 #pragma unroll
-    for (int e = 0; e < kPolMaxRows; ++e) pm[e] = ps[e] = 0.0f;
+    for (int e = 0; e < ROWS; ++e) pm[e] = ps[e] = 0.0f;
 #pragma nounroll
     for (int c = 0; c < n_slices; ++c) {
       const int nj = min(4, (H - 256 * c) >> 6), u0 = 256 * c + lane * nj;
-      float acc[kPolMaxRows][kJ];
+      float acc[ROWS][kJ];
       const float* b2 = blk(1);
 #pragma unroll
       for (int j = 0; j < kJ; ++j) {
         const float bj = j < nj ? b2[u0 + j] : 0.0f;
 #pragma unroll
-        for (int e = 0; e < kPolMaxRows; ++e) acc[e][j] = bj;
+        for (int e = 0; e < ROWS; ++e) acc[e][j] = bj;
       }
       for (int k = 0; k < H; k += 4) {
         float w[4][kJ];
@@ -1228,7 +1231,7 @@ __device__ __forceinline__ float policy_actions(bool want, const float ns[8], in
             for (int j = 0; j < kJ; ++j) w[kk][j] = j < nj ? CH.w2t[(size_t)(k + kk) * H + u0 + j] : 0.0f;
         }
 #pragma unroll
-        for (int e = 0; e < kPolMaxRows; ++e) {
+        for (int e = 0; e < ROWS; ++e) {
           if (e < E) {
             const float4 h4 = *reinterpret_cast<const float4*>(lds_h1 + e * kPolMaxHidden + k);
 #pragma unroll
@@ -1249,7 +1252,7 @@ __device__ __forceinline__ float policy_actions(bool want, const float ns[8], in
         wsj[j] = j < nj ? ws[u0 + j] : 0.0f;
       }
 #pragma unroll
-      for (int e = 0; e < kPolMaxRows; ++e) {
+      for (int e = 0; e < ROWS; ++e) {
 #pragma unroll
         for (int j = 0; j < kJ; ++j) {
           const float y = fmaxf(acc[e][j], 0.0f);
@@ -1263,7 +1266,7 @@ __device__ __forceinline__ float policy_actions(bool want, const float ns[8], in
     const uint64_t ctr = CH.pol_counter ? (uint64_t)*CH.pol_counter : 0;
     uint64_t m = rows;
 #pragma unroll
-    for (int e = 0; e < kPolMaxRows; ++e) {
+    for (int e = 0; e < ROWS; ++e) {
       if (e < E) {
         const int src = __ffsll((unsigned long long)m) - 1;
         m &= m - 1;
@@ -1438,11 +1441,26 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   static_assert(LPE >= 2 && (LPE & (LPE - 1)) == 0 && LPE <= 16, "LPE must be a power of two in [2, 16]");
   constexpr bool SIMPLE = COLLAV == SHIPSIM_COLLAV_SIMPLE;
   constexpr bool OPQ = LPE != 16 || POLICY || SLOTS > 2;  // see opaque_if (measured: LPE-16 two-slot table kernels hold no spills without)
+  // the K > 1 policy streams: the policy pass on top of the tightest env kernels. What else would sit in SGPRs
+  // across the tick loop (the env-leader mask, the want / stalled / started flags as lane masks, the scalar half
+  // of the route addresses, the ship count for the epilogue) is laundered or re-derived where it is used
+  constexpr bool OPM = POLICY && SLOTS > 2;
+  using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
+  // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
+  // instantiation compiles to the code it had (the dead arm of a constant condition is not emitted)
+#define OPM_GET(x) (OPM ? (decltype(x))opaque_v((int)(x)) : (x))
+#define OPM_SET(x, v)                                  \
+  {                                                    \
+    if constexpr (OPM) x = opaque_v((v) ? 1 : 0);      \
+    else x = (v);                                      \
+  }
   __shared__ ShipConst lds_sc[SHIPSIM_MAX_SHIPS];
   __shared__ EdgeX lds_edges[SHIPSIM_MAX_VERTS];
   __shared__ Edge lds_edges_raw[SHIPSIM_MAX_VERTS];
   __shared__ PolyBox lds_boxes[SHIPSIM_MAX_POLYS];
-  __shared__ float lds_pol[POLICY ? kPolMaxRows * kPolMaxHidden : 1];  // shipsim_run_policy: h1 rows
+  constexpr int kPolRows = SLOTS > 2 ? kPolMultiRows : kPolMaxRows;  // (64 / LPE <= 4 envs per wave with SLOTS > 2)
+  static_assert(SLOTS == 2 || 64 / LPE <= kPolMultiRows, "a policy pass serves every env of the wave");
+  __shared__ float lds_pol[POLICY ? kPolRows * kPolMaxHidden : 1];  // shipsim_run_policy: h1 rows
   __shared__ RewardTerm lds_rterm[8];  // the reward exp each lane of an env evaluates: its term's constants
   if constexpr (diag::kPoisonLds) {  // (stale-LDS diagnostics build only)
     diag::poison_lds(lds_sc, sizeof(lds_sc)); diag::poison_lds(lds_edges, sizeof(lds_edges));
@@ -1490,6 +1508,10 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   const ShipConst& c = SC[shipc];
   double* rn = S.route_n() + (size_t)qc * kMaxRoute;
   double* re = S.route_e() + (size_t)qc * kMaxRoute;
+  if constexpr (OPM) {  // whole addresses in VGPRs: no scalar base held for reset_env / decision_prologue
+    asm volatile("" : "+v"(rn));
+    asm volatile("" : "+v"(re));
+  }
 
   // (an int laundered where it is set, as have_iw: a bool here stayed a lane mask across the tick loop)
   int running = opaque_if<OPQ>((valid && (A0.active_mask == nullptr || A0.active_mask[envc]) && S.was_reset()[envc]) ? 1 : 0);
@@ -1525,7 +1547,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     for (int k = 0; k < 3; ++k) fuel[k] = T.fuel[(size_t)qc * 3 + k];
   }
   double out_r = 0.0;
-  bool out_done = false, stalled = false;
+  bool out_done = false;
+  flag_t stalled = false;
   int ready = 0;  // (an int: OPQ kernels keep it in a VGPR, not a lane mask merged across the tick loop)
   uint32_t out_bits = 0;
   int out_ticks = 0;
@@ -1539,13 +1562,13 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // ---- intermediate waypoint sampling (env.py:659-696) for an env that waits for a decision ----
   // CHAIN: episode / decision counters, decisions completed and records written in this call
   int ep_i = 0, dec_i = 0, n_decided = 0, log_n = 0;
-  bool started_here = false;  // POLICY: the decision in progress started in this launch (its record row holds
+  flag_t started_here = false;  // POLICY: the decision in progress started in this launch (its record row holds
                               // its action and observation-of-choice already)
   auto decision_prologue = [&](float sa, float a_log) __attribute__((always_inline)) {
     const StepArgs& A = step_args();
     const Params& P = A.P;
     const ConstBuf& K = A.K;
-    if (POLICY && lie == 0) {  // what the decision record will report: the action and the observation it saw,
+    if (POLICY && OPM_GET(lie) == 0) {  // what the decision record will report: the action and the observation it saw,
                                // into the record row it will complete in (stores only) and, for a decision
                                // that completes in a later launch, the state
       const DevState So = opaque(A.S);
@@ -1558,7 +1581,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         for (int i = 0; i < 8; ++i) rec[SHIPSIM_DL_OBS0 + i] = (double)ns[i];
       }
     }
-    started_here = true;
+    OPM_SET(started_here, true);
     if (P.normalize_action) sa = (sa + 1.0f) / 2.0f * (P.action_high - P.action_low) + P.action_low;
     phase = 0;
     have_iw = opaque_if<OPQ>(0);
@@ -1612,7 +1635,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     log_n = CH.log_len ? CH.log_len[envc] : 0;
     if (running && CH.log_stop && log_n >= CH.log_cap) {  // log already full: sit this launch out
       running = opaque_if<OPQ>(0);
-      stalled = (dflags & DF_AWAITING) != 0;
+      OPM_SET(stalled, (dflags & DF_AWAITING) != 0);
     }
   }
   auto table_action = [&]() __attribute__((always_inline)) -> float {
@@ -1667,7 +1690,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       return a_log;
     } else {
       const StepArgs& A = step_args();
-      a_log = policy_actions(want, ns, envc, lie == 0, env_lane0, n_decided, A.CH, lds_pol);
+      a_log = policy_actions<kPolRows>(want, ns, envc, OPM_GET(lie) == 0, env_lane0, n_decided, A.CH, lds_pol);
       const Params& P = A.P;
       const float lb = P.normalize_action ? -1.0f : P.action_low, ub = P.normalize_action ? 1.0f : P.action_high;
       return denormalize_f32(a_log, lb, ub);  // NormalizedBoxEnv in front of the env
@@ -1682,7 +1705,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // wave-uniform (the policy is evaluated by the whole wave); with the table each env loops on its own.
   auto chain_next = [&]() __attribute__((always_inline)) {
     for (int burst = 0; POLICY ? __any(ready && running) : (ready && running); ++burst) {
-      bool want = false;
+      flag_t want = false;
       if (ready && running) {
         const ChainArgs& CH = step_args().CH;
         if (CH.log && opaque_if<OPQ>(lie) == 0 && log_n < CH.log_cap) {
@@ -1691,7 +1714,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
           rec[SHIPSIM_DL_DONE] = out_done ? 1.0 : 0.0; rec[SHIPSIM_DL_EPISODE] = (double)ep_i;
           rec[SHIPSIM_DL_DECISION] = (double)dec_i; rec[SHIPSIM_DL_TICKS] = (double)out_ticks;
           for (int i = 0; i < 8; ++i) rec[SHIPSIM_DL_OBS + i] = (double)ns[i];
-          if (POLICY && !started_here) {  // started in an earlier launch: from the state
+          if (POLICY && !OPM_GET(started_here)) {  // started in an earlier launch: from the state
             const DevState So = opaque(step_args().S);
             rec[SHIPSIM_DL_ACTION] = (double)So.dec_action()[envc];
             for (int i = 0; i < 8; ++i) rec[SHIPSIM_DL_OBS0 + i] = (double)So.dec_obs0()[envc * 8 + i];
@@ -1699,7 +1722,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         }
         log_n += 1;
         n_decided += 1;
-        started_here = false;
+        OPM_SET(started_here, false);
         if (out_done || dec_i + 1 >= CH.n_dec) {
           reset_env();
           ep_i += 1;
@@ -1714,24 +1737,25 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         ready = opaque_if<OPQ>(0);
         out_done = false;
         if (burst + 1 >= kChainBurst || (CH.log_stop && log_n >= CH.log_cap)) {
-          stalled = true;  // next decision pending: resumed by the next launch
+          OPM_SET(stalled, true);  // next decision pending: resumed by the next launch
           running = opaque_if<OPQ>(0);
         } else {
-          want = true;
+          OPM_SET(want, true);
         }
       }
       float a_log;
       const float sa = chain_action(want, a_log);
-      if (want) decision_prologue(sa, a_log);
+      if (OPM_GET(want)) decision_prologue(sa, a_log);
     }
   };
 
   {
-    const bool want = running && (dflags & DF_AWAITING);
+    const flag_t want = OPM ? (flag_t)opaque_v((running && (dflags & DF_AWAITING)) ? 1 : 0)
+                            : (flag_t)(running && (dflags & DF_AWAITING));
     if (CHAIN) {
       float a_log;
       const float sa = chain_action(want, a_log);
-      if (want) decision_prologue(sa, a_log);
+      if (OPM_GET(want)) decision_prologue(sa, a_log);
     } else if (want) {
       decision_prologue(A0.action[envc], A0.action[envc]);
     }
@@ -2149,7 +2173,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         ready = opaque_if<OPQ>(1);
       }
       const int mt = OPQ ? opaque_v(budget) : budget;  // (OPQ: its test not held across the loop)
-      going = opaque_if<OPQ>((!ready && (mt <= 0 || ticks < mt)) ? 1 : 0);
+      going = opaque_if<OPQ>((!OPM_GET(ready) && (mt <= 0 || ticks < mt)) ? 1 : 0);
     }
     PT_MARK(3);
   }
@@ -2157,7 +2181,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   if (POLICY || (ready && running)) chain_next();  // (policy: wave-uniform, a no-op unless a decision completed)
   {
     const int mt = OPQ ? opaque_v(budget) : budget;
-    going = opaque_if<OPQ>((running && !ready && (mt <= 0 || ticks < mt)) ? 1 : 0);
+    going = opaque_if<OPQ>((running && !OPM_GET(ready) && (mt <= 0 || ticks < mt)) ? 1 : 0);
   }
   if (!__any(opaque_if<OPQ>(going))) {
     // Launch tail: this wave's envs met the quota. While any wave of the launch has not, keep ticking in chunks
@@ -2188,10 +2212,11 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   const Traj& TE = AE.T;
   SHIPSIM_DEBUG_PRINT(env, "[dbg] env %d lie %d end: ready %d ticks %d sc %d n_base %f phase %d have_iw %d\n", env, lie,
                       (int)ready, ticks, sampling_count, n_base, phase, (int)have_iw);
+  if constexpr (OPM) ready = opaque_v(ready);  // (tested from the VGPR below: no ready / !ready masks kept from the loop)
   const DevState So = opaque(AE.S);  // addresses recomputed here, not carried through the loop
   // the lane's role re-derived here (opaque), not lane masks carried through the loop
   const int lie_e = opaque_v(lie), sub_e = lie_e / SLOTS, ship_e = lie_e % SLOTS;
-  const bool ghost_e = (SLOTS > 2) && ship_e >= nsh;
+  const bool ghost_e = (SLOTS > 2) && ship_e >= (OPM ? AE.P.n_ships : nsh);
   if (sub_e == 0 && !ghost_e) store_ship(So, qc, s);
   if (REC) {
     if (sub_e == 0)
@@ -2215,7 +2240,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     if (ready)
       for (int i = 0; i < 8; ++i) So.next_obs8()[env * 8 + i] = ns[i];
     So.snap_bits()[env] = snap_bits;
-    So.dec_flags()[env] = ((ready || stalled) ? DF_AWAITING : 0) | (have_iw ? DF_HAVE_IW : 0) |
+    So.dec_flags()[env] = ((ready || OPM_GET(stalled)) ? DF_AWAITING : 0) | (have_iw ? DF_HAVE_IW : 0) |
                           (phase << DF_PHASE_SHIFT);
     So.dec_ticks()[env] = dec_ticks;
     if (n_nonfinite) atomicAdd(So.nonfinite, n_nonfinite);
@@ -2232,6 +2257,9 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     for (int i = 0; i < 8; ++i) AE.obs_out[env * 8 + i] = ns[i];
   }
 }
+
+#undef OPM_GET
+#undef OPM_SET
 
 // C2 single-ship loop body, k ticks per launch (one lane per ship; algebraic wind force)
 template <bool DETAILED>
@@ -3623,24 +3651,27 @@ static int run_chain(shipsim_handle* h, const ChainArgs& ch, int32_t max_ticks, 
 #if SHIPSIM_REGCHECK == 2  // the LPE-8 stream kernels (the C4 shard's collector)
   if (det) CHAINED_L(true, SHIPSIM_COLLAV_SBMPC, 8);
   else CHAINED_L(false, SHIPSIM_COLLAV_SBMPC, 8);
-#elif SHIPSIM_REGCHECK == 3  // the multi-obstacle decision stream
+#elif SHIPSIM_REGCHECK == 3  // the multi-obstacle decision streams (table: sbmpc; policy: sbmpc and none)
   (void)det;
-  if (MODE == 1)
-    launch_multi<SHIPSIM_COLLAV_SBMPC, 1>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr, ticks_out,
-                                          nullptr, ch);
+  if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
+    launch_multi<SHIPSIM_COLLAV_SBMPC, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
+                                             ticks_out, nullptr, ch);
+  else if (MODE == 2)
+    launch_multi<SHIPSIM_COLLAV_NONE, 2>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr, ticks_out,
+                                         nullptr, ch);
 #else
   if (h->P.collav == SHIPSIM_COLLAV_SBMPC) CHAINED_L(true, SHIPSIM_COLLAV_SBMPC, 16);
   else CHAINED_L(true, SHIPSIM_COLLAV_NONE, 16);
   (void)det;
 #endif
 #else
-  if (MODE == 1 && ship_slots(h) > 2) {  // (run_policy refuses K > 1 before it gets here)
+  if (ship_slots(h) > 2) {  // K > 1 obstacle ships (collav none / sbmpc: shipsim_create); no launch tail
     if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
-      launch_multi<SHIPSIM_COLLAV_SBMPC, 1>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
-                                            ticks_out, nullptr, ch);
+      launch_multi<SHIPSIM_COLLAV_SBMPC, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
+                                               ticks_out, nullptr, ch);
     else
-      launch_multi<SHIPSIM_COLLAV_NONE, 1>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
-                                           ticks_out, nullptr, ch);
+      launch_multi<SHIPSIM_COLLAV_NONE, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
+                                              ticks_out, nullptr, ch);
     HIPCHK(h, hipGetLastError());
     return SHIPSIM_OK;
   }
@@ -3684,7 +3715,6 @@ int shipsim_run_policy(shipsim_handle* h, const float* policy, const float* w2t,
   if (obs_dim != 8) return fail(h, SHIPSIM_EINVAL, "run_policy: observation dim %d (the AST observation has 8)", obs_dim);
   if (hidden < 64 || hidden > kPolMaxHidden || hidden % 64)
     return fail(h, SHIPSIM_EINVAL, "run_policy: hidden %d (a multiple of 64 up to 512)", hidden);
-  if (ship_slots(h) > 2) return fail(h, SHIPSIM_EINVAL, "run_policy: one obstacle ship only");
   ChainArgs ch = {};
   ch.n_eps = 1; ch.n_dec = n_dec; ch.ep_idx = ep_idx; ch.dec_idx = dec_idx;
   ch.decisions = decisions_out; ch.log = log; ch.log_len = log_len; ch.log_cap = log_cap;

@@ -28,9 +28,11 @@ OBS_HIGH = np.array([10000, 20000, 3000, 10000, 20000, np.pi, 3000, 10], dtype=n
 
 
 def default_args(**kw):
-    """run/ast-sac_runner.py:27-43 defaults (environment group)."""
+    """run/ast-sac_runner.py:27-43 defaults (environment group). n_obs_ships (beyond the reference): obstacle
+    ships per env, 1..abi.MAX_OBS; K > 1 adds abi.TRAFFIC_SHIPS[:K-1] as ships 2..K."""
     a = dict(max_sampling_frequency=9, time_step=4, radius_of_acceptance=300, lookahead_distance=1000,
-             collav_mode="sbmpc", ship_draw=False, time_since_last_ship_drawing=30, normalize_action=False)
+             collav_mode="sbmpc", ship_draw=False, time_since_last_ship_drawing=30, normalize_action=False,
+             n_obs_ships=1)
     a.update(kw)
     return argparse.Namespace(**a)
 
@@ -39,7 +41,8 @@ def config_from_args(args, machinery="detailed"):
     """The scenario of record (run/env_setup.py) with the env arguments applied."""
     mach = abi.MACH_DETAILED if machinery in ("detailed", abi.MACH_DETAILED) else abi.MACH_SIMPLIFIED
     collav = getattr(args, "collav_mode", "sbmpc")
-    cfg = abi.ast_config(collav if collav in abi.COLLAV else "none", time_step=float(args.time_step), machinery=mach)
+    cfg = abi.ast_config(collav if collav in abi.COLLAV else "none", time_step=float(args.time_step), machinery=mach,
+                         n_obs_ships=int(getattr(args, "n_obs_ships", 1)))
     cfg.max_sampling_frequency = int(args.max_sampling_frequency)
     cfg.env_radius_of_acceptance = float(args.radius_of_acceptance)
     for s in cfg.ship:
@@ -56,7 +59,8 @@ class BatchedMultiShipRLEnv:
         if lanes_per_env:
             self.cfg.lanes_per_env = lanes_per_env
         self.n_envs = int(n_envs)
-        self.sim = ShipSim(self.cfg, self.n_envs, device=device)
+        self.n_obs_ships = int(self.cfg.n_ships) - 1  # K obstacle ships per env (1: the reference's env)
+        self.sim = ShipSim(self.cfg, self.n_envs, device=device, n_obs_ships=self.n_obs_ships)
         self.device = self.sim.device
         self.collav = getattr(self.args, "collav_mode", "sbmpc")
         self.observation_space = Box(low=OBS_LOW, high=OBS_HIGH, dtype=np.float32)
@@ -109,10 +113,12 @@ class BatchedMultiShipRLEnv:
         return self.sim.get(abi.E_SAMPLING_COUNT)
 
     def obstacle_routes(self):
-        """(N, L, 2) obstacle-ship route (north, east) incl. sampled intermediate waypoints."""
-        n = self.sim.get(abi.E_ROUTE_NORTH).view(self.n_envs, 2, abi.MAX_ROUTE)[:, 1]
-        e = self.sim.get(abi.E_ROUTE_EAST).view(self.n_envs, 2, abi.MAX_ROUTE)[:, 1]
-        L = self.sim.get(abi.E_ROUTE_LEN).view(self.n_envs, 2)[:, 1]
+        """(N, L, 2) route (north, east) of the obstacle ship (ship 1: the one the waypoints are sampled for,
+        whatever the number of obstacle ships) incl. sampled intermediate waypoints."""
+        ns = self.sim.n_ships
+        n = self.sim.get(abi.E_ROUTE_NORTH).view(self.n_envs, ns, abi.MAX_ROUTE)[:, 1]
+        e = self.sim.get(abi.E_ROUTE_EAST).view(self.n_envs, ns, abi.MAX_ROUTE)[:, 1]
+        L = self.sim.get(abi.E_ROUTE_LEN).view(self.n_envs, ns)[:, 1]
         return torch.stack([n, e], -1), L
 
     def seed(self, seed=None):
@@ -127,7 +133,9 @@ class BatchedMultiShipRLEnv:
     def record_trajectories(self, capacity=None):
         """Record every tick of every env (both ships' simulation_results rows + RewardTracker rows)
         into device buffers; rows start at the next reset. capacity defaults to the longest episode
-        (simulation_time / time_step + 2 rows)."""
+        (simulation_time / time_step + 2 rows). One obstacle ship only (the recording kernels are two-ship)."""
+        if self.n_obs_ships > 1:
+            raise ValueError(f"trajectory recording needs one obstacle ship per env (this env has {self.n_obs_ships})")
         if capacity is None:
             capacity = int(np.ceil(self.cfg.simulation_time / self.cfg.time_step)) + 8
         return self.sim.set_trajectory(capacity)
@@ -143,10 +151,13 @@ class BatchedMultiShipRLEnv:
 
     # snapshots (logger.save_itr_params pickles the collectors' env): keep the config, not the device state
     def __getstate__(self):
-        return dict(args=self.args, cfg=bytes(self.cfg), n_envs=self.n_envs, device=str(self.device))
+        return dict(args=self.args, cfg=bytes(self.cfg), n_envs=self.n_envs, device=str(self.device),
+                    n_obs_ships=self.n_obs_ships)
 
     def __setstate__(self, st):
         cfg = abi.Config.from_buffer_copy(st["cfg"])
+        if "n_obs_ships" in st:  # (the config carries it too; older snapshots have one obstacle ship)
+            cfg.n_ships = 1 + int(st["n_obs_ships"])
         self.__init__(st["args"], st["n_envs"], device=st["device"], cfg=cfg)
 
 
@@ -239,8 +250,12 @@ class MultiShipRLEnv:
     def __init__(self, args=None, device=None, machinery="detailed", cfg=None, assets=None, map=None,
                  record_trajectory=False, trajectory_capacity=None):
         self.args = args if args is not None else default_args()
-        self._b = BatchedMultiShipRLEnv(self.args, 1, device=device, machinery=machinery, cfg=cfg)
         self.record_trajectory = bool(record_trajectory)
+        k_obs = int(cfg.n_ships) - 1 if cfg is not None else int(getattr(self.args, "n_obs_ships", 1))
+        if self.record_trajectory and k_obs > 1:  # (before the device env exists)
+            raise ValueError(f"record_trajectory=True needs one obstacle ship (the recording kernels and the "
+                             f"[test, obs] views are two-ship); this env has {k_obs}")
+        self._b = BatchedMultiShipRLEnv(self.args, 1, device=device, machinery=machinery, cfg=cfg)
         if self.record_trajectory:
             self._b.record_trajectories(trajectory_capacity)
         self.test, self.obs = ShipAssetView(self, 0), ShipAssetView(self, 1)

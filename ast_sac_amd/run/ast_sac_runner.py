@@ -6,7 +6,8 @@ Same CLI and variant as the reference. Two execution shapes:
   NormalizedBoxEnv, MdpPathCollector(ast_sac_rollout), EnvReplayBuffer, SACTrainer,
   TorchBatchRLAlgorithm — for drop-in use and side-by-side comparison.
 * `--n_envs N` (default 4096): the MI355X shape — N device-resident envs per GPU stepped in
-  slices, transitions written straight into a DeviceReplayBuffer, FusedSACTrainer (HIP-graph
+  slices (`--obs_ships K`, K = 2..4: the multi-obstacle scenario, this shape only), transitions written straight
+  into a DeviceReplayBuffer, FusedSACTrainer (HIP-graph
   step) and DeviceBatchRLAlgorithm. Under torch.distributed.run every rank owns N envs. With
   --dp_mode replicated (default) every rank keeps the union of all ranks' transitions (RCCL
   all-gathers of the row counts and the new rows once per train loop) and runs the same global-batch SAC step, so no
@@ -84,13 +85,33 @@ def build_parser():
                         "row all-gather (after a count all-gather) per train loop, no per-step collective); allreduce = local buffers, one gradient "
                         "all-reduce per grad step")
     p.add_argument("--machinery", type=str, default="detailed", choices=["detailed", "simplified"])
+    p.add_argument("--obs_ships", dest="n_obs_ships", type=int, default=1, metavar="K",
+                   help="obstacle ships per env (1: the reference's scenario). K = 2..4 is the multi-obstacle C5 "
+                        "scenario: shipsim_abi.TRAFFIC_SHIPS[:K-1] sail as ships 2..K (the policy still places ship "
+                        "1's waypoints; the ship under test avoids all of them). Needs --machinery detailed, "
+                        "--collav_mode sbmpc or none, and --n_envs > 0")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--log_dir", type=str, default=None)
     return p
 
 
 def parse_cli_args(argv=None):
-    return build_parser().parse_args(argv)
+    from .. import shipsim_abi as abi
+    p = build_parser()
+    args = p.parse_args(argv)
+    k = args.n_obs_ships
+    if not 1 <= k <= abi.MAX_OBS:
+        p.error(f"--obs_ships {k}: 1..{abi.MAX_OBS} obstacle ships")
+    if k > 1:  # what shipsim_create refuses for K > 1, said here with the reason
+        if args.machinery != "detailed":
+            p.error(f"--obs_ships {k} needs --machinery detailed: the multi-obstacle env kernels are built for the "
+                    "detailed machinery only")
+        if args.collav_mode == "simple":
+            p.error(f"--obs_ships {k} needs --collav_mode sbmpc or none: the simple collision avoidance reads one "
+                    "obstacle ship")
+        if args.n_envs <= 0:
+            p.error(f"--obs_ships {k} needs --n_envs > 0: the reference single-env graph unpacks [test, obs]")
+    return args
 
 
 def make_variant(args):
@@ -108,6 +129,7 @@ def make_variant(args):
                             use_automatic_entropy_tuning=args.use_automatic_entropy_tuning,
                             action_reg_coeff=args.action_reg_coeff, clip_val=args.clip_val),
         n_envs=args.n_envs, slice_ticks=args.slice_ticks, machinery=args.machinery,
+        n_obs_ships=getattr(args, "n_obs_ships", 1),
         match_update_ratio=args.match_update_ratio, dp_mode=args.dp_mode)
 
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SHIPSIM_ABI_VERSION 10
+#define SHIPSIM_ABI_VERSION 11  /* 11: shipsim_run_policy runs K > 1 obstacle ships */
 
 #define SHIPSIM_MAX_ROUTE 16   /* waypoints per ship route (obs ship: 2 + max_sampling_frequency) */
 #define SHIPSIM_MAX_POLYS 16   /* land polygons in the map */
@@ -434,7 +434,8 @@ int shipsim_run_table(shipsim_handle* h, const float* table, int32_t n_eps, int3
  *            decision record's SHIPSIM_DL_ACTION column holds the normalized action a in (-1, 1).
  *            With a log, an env stops for the launch once it holds log_cap records (log_len starts where
  *            the caller left it), its next decision pending for the next call: no record is lost.
- * One obstacle ship only (SHIPSIM_EINVAL otherwise, as for a bad obs_dim / hidden). */
+ * K obstacle ships as for shipsim_run_table (ABI 11): K > 1 with the detailed machinery and collav none or sbmpc,
+ * as shipsim_create requires. SHIPSIM_EINVAL for a bad obs_dim / hidden. */
 int shipsim_run_policy(shipsim_handle* h, const float* policy, const float* w2t, int32_t obs_dim, int32_t hidden,
                        int32_t deterministic, uint64_t seed, const int64_t* counter, int32_t n_dec,
                        int32_t max_ticks, int32_t* ep_idx, int32_t* dec_idx, int32_t* ticks_out,

@@ -2,7 +2,7 @@
 #   bash scripts/regcheck.sh [N] [extra hipcc flags]   libshipsim with -DSHIPSIM_REGCHECK=N (one kernel set):
 #     N = 1 (default): the headline stream kernels (chained, LPE 16, detailed; sbmpc and none)
 #     N = 2: the LPE-8 stream kernels (the C4 shard's collector: policy and table streams)
-#     N = 3: the multi-obstacle (K > 1) step kernels
+#     N = 3: the multi-obstacle (K > 1) kernels: steps, table streams and policy streams (collav none and sbmpc)
 #   bash scripts/regcheck.sh sac H [extra hipcc flags]   libsacfused's kernels of hidden width H only
 set -e
 cd "$(dirname "$0")/.."
