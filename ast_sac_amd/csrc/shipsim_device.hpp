@@ -95,6 +95,15 @@ struct Params {
   double wind_sin, wind_cos, iw_cos, iw_sin;
 };
 
+// Per-env weather (shipsim_set_weather): what the AST tick reads of the weather, as lane values loaded once per
+// launch. Field names are Params' own, so the ship model's expressions are written once for both.
+struct LaneWeather {
+  double vc_n, vc_e, wind_speed, wind_sin, wind_cos;
+};
+// the device array behind it: kWeatherCols columns of n_envs doubles each
+constexpr int kWeatherCols = 5;
+enum { WX_WIND_SPEED = 0, WX_WIND_SIN = 1, WX_WIND_COS = 2, WX_VC_N = 3, WX_VC_E = 4 };
+
 // Map edges (obstacle.py PolygonObstacle). Stored as a flat read-only device table; every lane
 // walks it with the same (wave-uniform) index, so loads are scalar/broadcast.
 struct Edge {
@@ -237,7 +246,9 @@ __device__ __forceinline__ void wind_force(const ShipConst& c, const Params& P, 
 // cos(gamma) = u_rw / V, sin(gamma) = -v_rw / V, sin(2 gamma) = -2 u_rw v_rw / V^2, so
 //   tau = (-0.5 rho cx A_f u_rw V, -0.5 rho cy A_l v_rw V, -rho cn A_l L u_rw v_rw):
 // one sqrt instead of atan2 and three sincos; equal to wind_force up to rounding (V = 0 gives 0).
-__device__ __forceinline__ void wind_force_alg(const ShipConst& c, const Params& P, const Ship& s, double sy,
+// W: where the weather is read from — Params (wave-uniform, the config's) or LaneWeather (per env).
+template <class W>
+__device__ __forceinline__ void wind_force_alg(const ShipConst& c, const W& P, const Ship& s, double sy,
                                                double cy, double wsin, double wcos, double tau[3]) {
   if constexpr (diag::kNoWind) {  // (ablation build only)
     tau[0] = tau[1] = tau[2] = 0.0;
@@ -258,7 +269,9 @@ __device__ __forceinline__ void wind_force_alg(const ShipConst& c, const Params&
 // three_dof_kinematics :519-528, shaft_eq + thrust (ship_engine.py:403-443), three_dof_kinetics
 // :834-864 with rudder :866-880. `ctrl` is the engine throttle (detailed) or thrust force (simplified);
 // (sy, cy) = sin/cos(yaw), tau = get_wind_force.
-__device__ __forceinline__ Deriv differentials_body(const ShipConst& c, const Params& P, const Ship& s, double ctrl,
+// W: as wind_force_alg (the current's two components).
+template <class W>
+__device__ __forceinline__ Deriv differentials_body(const ShipConst& c, const W& P, const Ship& s, double ctrl,
                                                     double delta, bool detailed, double sy, double cy,
                                                     const double tau[3]) {
   Deriv d;
@@ -323,7 +336,9 @@ __device__ __forceinline__ Deriv differentials(const ShipConst& c, const Params&
 // differentials of the AST kernels: (sy, cy) = sin/cos(yaw) carried from the previous integration
 // step (the kernels evaluate it once per tick, after integrating, and reuse it for the encounter
 // angle of the reward), algebraic wind force with the host-evaluated sin/cos(wind_direction).
-__device__ __forceinline__ Deriv differentials_sc(const ShipConst& c, const Params& P, const Ship& s, double ctrl,
+// W: Params, or the env's LaneWeather in the per-env weather kernels (the same expressions on lane values).
+template <class W>
+__device__ __forceinline__ Deriv differentials_sc(const ShipConst& c, const W& P, const Ship& s, double ctrl,
                                                   double delta, bool detailed, double sy, double cy) {
   double tau[3];
   wind_force_alg(c, P, s, sy, cy, P.wind_sin, P.wind_cos, tau);

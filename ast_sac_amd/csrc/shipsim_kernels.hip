@@ -22,11 +22,16 @@
 
 #include "shipsim.h"
 #include "shipsim_device.hpp"
+#include "shipsim_weather_host.hpp"  // shipsim_set_weather's host half
 
 #include "shipsim_diag.hpp"  // diagnostics / ablation hooks (none in the product build)
 
 
 using namespace shipsim;
+static_assert(kWeatherCols == weather_host::kCols && WX_WIND_SPEED == weather_host::kWindSpeed &&
+                  WX_WIND_SIN == weather_host::kWindSin && WX_WIND_COS == weather_host::kWindCos &&
+                  WX_VC_N == weather_host::kCurrentN && WX_VC_E == weather_host::kCurrentE,
+              "the weather array's columns: device and host agree");
 
 // Translation-unit role (ast_sac_amd/build_hash.py OBJECTS):
 //   SHIPSIM_TU 1: every kernel but single_tick_pipe_kernel, and the C ABI — built without machine-level LICM (the
@@ -271,8 +276,9 @@ __device__ __forceinline__ void control_and_integrate(const ShipConst& c, const 
 // the same tick in the AST kernels (step, decision stream, reset / init_step): algebraic wind force
 // and sin/cos(yaw) carried in (sy, cy) — valid for s.yaw on entry, refreshed after the integration
 // step, so one sincos per ship-tick serves both the kinematics and the reward's encounter angle.
-template <bool DETAILED, bool REC = false, bool PRE = false>
-__device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, const Params& P, Ship& s,
+// W: the weather's source, Params or the env's LaneWeather (differentials_sc).
+template <bool DETAILED, bool REC = false, bool PRE = false, class W = Params>
+__device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, const Params& P, const W& wx, Ship& s,
                                                          const double* __restrict__ rn,
                                                          const double* __restrict__ re, double offset,
                                                          double speed_factor, double mach_dt, int simple_collav_flag,
@@ -281,7 +287,7 @@ __device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, con
   double ctrl, rudder;
   control_and_store<DETAILED, REC, PRE>(c, P, s, rn, re, offset, speed_factor, mach_dt, simple_collav_flag, imminent,
                                         row, fuel, ctrl, rudder, pre_q, pre_e);
-  Deriv d = differentials_sc(c, P, s, ctrl, rudder, DETAILED, sy, cy);
+  Deriv d = differentials_sc(c, wx, s, ctrl, rudder, DETAILED, sy, cy);
   integrate(s, d, P.dt, mach_dt, DETAILED);
   sincos(s.yaw, &sy, &cy);
 }
@@ -945,6 +951,22 @@ __global__ void init_kernel(const Params P, DevState S, ConstBuf K) {
   }
 }
 
+// Per-env weather (shipsim_set_weather) in the AST kernels. WX kernels read the five values of the lane's env
+// once per launch from the handle's weather array (load_weather) and hold them in registers; every other kernel
+// reads Params where the value is used, as before (weather_of picks the source at compile time, so the uniform
+// kernels see the expressions they always had and compile to the code they had).
+struct NoWeather {};
+__device__ __forceinline__ const Params& weather_of(const Params& P, const NoWeather&) { return P; }
+__device__ __forceinline__ const LaneWeather& weather_of(const Params&, const LaneWeather& w) { return w; }
+__device__ __forceinline__ void load_weather(NoWeather&, const double*, int, int) {}
+__device__ __forceinline__ void load_weather(LaneWeather& w, const double* __restrict__ wx, int n_envs, int env) {
+  w.wind_speed = wx[(size_t)WX_WIND_SPEED * n_envs + env];
+  w.wind_sin = wx[(size_t)WX_WIND_SIN * n_envs + env];
+  w.wind_cos = wx[(size_t)WX_WIND_COS * n_envs + env];
+  w.vc_n = wx[(size_t)WX_VC_N * n_envs + env];
+  w.vc_e = wx[(size_t)WX_VC_E * n_envs + env];
+}
+
 // MultiShipRLEnv.reset (env.py:238-295): reset assets + IW sampler + snapshot, then init_step
 template <bool DETAILED, bool REC>
 __global__ __launch_bounds__(256) void reset_kernel(const Params P, DevState S, ConstBuf K, Traj T,
@@ -976,13 +998,60 @@ __global__ __launch_bounds__(256) void reset_kernel(const Params P, DevState S, 
   double fuel[3] = {0.0, 0.0, 0.0};  // machinery reset restores the fuel accumulators (ship_engine.py:468-481)
   double sy, cy;
   sincos(s.yaw, &sy, &cy);
-  control_and_integrate_sc<DETAILED, REC>(c, P, s, rn, re, 0.0, 1.0, mach_dt, 0, false,
+  control_and_integrate_sc<DETAILED, REC>(c, P, P, s, rn, re, 0.0, 1.0, mach_dt, 0, false,
                                           REC ? T.ship_row(q, 0) : nullptr, fuel, sy, cy);
   store_ship(S, q, s);
   if (REC) {
     for (int k = 0; k < 3; ++k) T.fuel[(size_t)q * 3 + k] = fuel[k];
     if (ship == 0) T.len[env] = 1;
   }
+  if (ship == 0) {
+    S.sampling_count()[env] = 0;
+    S.travel_dist()[env] = 0; S.travel_time()[env] = 0; S.acc()[env] = 0;
+    S.n_base()[env] = P.n_base0; S.e_base()[env] = P.e_base0;
+    S.mach_dt()[env] = mach_dt;
+    for (int i = 0; i < 8; ++i) S.next_obs8()[env * 8 + i] = P.initial_states[i];
+    S.snap_bits()[env] = 0;
+    S.was_reset()[env] = 1;
+    S.dec_flags()[env] = DF_AWAITING;
+    if (obs_out)
+      for (int i = 0; i < 8; ++i) obs_out[env * 8 + i] = P.initial_states[i];
+  }
+}
+
+// reset_kernel for a handle with per-env weather (detailed machinery, no recording: shipsim_set_weather): the
+// same statements, the init_step under the env's weather. Its own kernel, so that reset_kernel stays the code it was.
+__global__ __launch_bounds__(256) void reset_wx_kernel(const Params P, DevState S, ConstBuf K, const uint8_t* mask,
+                                                      float* obs_out, const double* __restrict__ wx) {
+  __shared__ ShipConst lds_sc[SHIPSIM_MAX_SHIPS];
+  const ShipConst* SC = stage_consts(K, lds_sc, P.n_ships, P.dt);
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int nq = P.n_envs * P.n_ships;
+  if (q >= nq) return;
+  const int ship = q % P.n_ships;
+  const int env = q / P.n_ships;
+  if (mask && !mask[env]) return;
+  const ShipConst& c = SC[ship];
+  Ship s;
+  s.n = c.init_n; s.e = c.init_e; s.yaw = c.init_yaw; s.u = c.init_u; s.v = c.init_v; s.r = c.init_r;
+  s.omega = c.init_omega; s.time = 0.0;
+  s.e_ct = 0; s.e_ct_int = 0; s.hdg_ei = 0; s.hdg_prev = 0;
+  s.spd_a = 0; s.spd_b = c.init_shaft_ei;
+  s.next_wpt = 1; s.stop = 0; s.n_route = c.n_route;
+  double* rn = S.route_n() + (size_t)q * kMaxRoute;
+  double* re = S.route_e() + (size_t)q * kMaxRoute;
+  for (int i = 0; i < c.n_route; ++i) {
+    rn[i] = K.cfg_route_n()[ship * kMaxRoute + i];
+    re[i] = K.cfg_route_e()[ship * kMaxRoute + i];
+  }
+  load_segment(s, rn, re);
+  const double mach_dt = P.mach_dt_reset;
+  double sy, cy;
+  sincos(s.yaw, &sy, &cy);
+  LaneWeather lw;
+  load_weather(lw, wx, P.n_envs, env);
+  control_and_integrate_sc<true, false>(c, P, lw, s, rn, re, 0.0, 1.0, mach_dt, 0, false, nullptr, nullptr, sy, cy);
+  store_ship(S, q, s);
   if (ship == 0) {
     S.sampling_count()[env] = 0;
     S.travel_dist()[env] = 0; S.travel_time()[env] = 0; S.acc()[env] = 0;
@@ -1397,6 +1466,7 @@ struct StepArgs {
   uint8_t* ready_out;
   ChainArgs CH;
   int32_t max_ticks;
+  const double* weather;  // WX kernels: the handle's per-env weather array (kWeatherCols x n_envs), else unread
 };
 typedef const __attribute__((address_space(4))) StepArgs* StepArgsPtr;
 __device__ __forceinline__ const StepArgs& step_args() {
@@ -1424,9 +1494,16 @@ __device__ __forceinline__ const StepArgs& step_args() {
 // SLOTS (2, 4, 8): ship slots per env. 2 is the reference's two-ship env (lane & 1 = ship); with
 // K > 1 obstacle ships (shipsim_create) ship k sits on the lanes of index k mod SLOTS, and slots past
 // the env's last ship repeat that ship (ghost lanes: same state and arithmetic, never stored).
-template <bool DETAILED, int COLLAV, int LPE, bool REC, int CHAIN = 0, int SLOTS = 2>
+// MODE: CHAIN (0 shipsim_step, 1 shipsim_run_table, 2 shipsim_run_policy), plus kStepWeather for the kernels of a
+// handle with per-env weather (shipsim_set_weather): MODE 4, 5, 6. (One parameter for both, so that the kernels
+// without weather keep the names, and the code, they had.)
+constexpr int kStepWeather = 4;
+template <bool DETAILED, int COLLAV, int LPE, bool REC, int MODE = 0, int SLOTS = 2>
 __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
-  constexpr bool POLICY = CHAIN == 2;  // CHAIN: 0 shipsim_step, 1 shipsim_run_table, 2 shipsim_run_policy
+  constexpr int CHAIN = MODE & 3;
+  constexpr bool WX = (MODE & kStepWeather) != 0;
+  static_assert(CHAIN <= 2 && MODE < 2 * kStepWeather, "MODE: CHAIN | kStepWeather");
+  constexpr bool POLICY = CHAIN == 2;
   (void)A_arg;  // read through step_args() only (see StepArgs)
   const StepArgs& A0 = step_args();
   const Params& P = A0.P;
@@ -1436,6 +1513,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   const int max_ticks = A0.max_ticks;
   static_assert(!(REC && CHAIN), "trajectory recording runs the per-decision step only");
   static_assert(SLOTS == 2 || (LPE == 16 && !REC && COLLAV != SHIPSIM_COLLAV_SIMPLE), "multi-obstacle layout");
+  static_assert(!WX || (DETAILED && !REC && COLLAV != SHIPSIM_COLLAV_SIMPLE), "per-env weather kernels");
   constexpr int NSUB = LPE / SLOTS;
   static_assert(NSUB >= 1 && 8 % NSUB == 0, "sub-lanes per ship must divide 8 (grid_part shares)");
   static_assert(LPE >= 2 && (LPE & (LPE - 1)) == 0 && LPE <= 16, "LPE must be a power of two in [2, 16]");
@@ -1522,6 +1600,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   load_ship(S, qc, s);
   double sy, cy;  // sin/cos(s.yaw), refreshed by every integration step
   sincos(s.yaw, &sy, &cy);
+  std::conditional_t<WX, LaneWeather, NoWeather> lw;  // WX: this env's weather for the whole launch
+  load_weather(lw, A0.weather, P.n_envs, envc);
   int sampling_count = S.sampling_count()[envc];
   double travel_dist = S.travel_dist()[envc], travel_time = S.travel_time()[envc], acc = S.acc()[envc];
   double n_base = S.n_base()[envc], e_base = S.e_base()[envc];
@@ -1663,8 +1743,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     load_segment(s, rn, re);
     mach_dt = P.mach_dt_reset;
     sincos(s.yaw, &sy, &cy);
-    control_and_integrate_sc<DETAILED, false>(c, P, s, rn, re, 0.0, 1.0, mach_dt, 0, false, nullptr, nullptr, sy,
-                                              cy);  // init_step
+    control_and_integrate_sc<DETAILED, false>(c, P, weather_of(P, lw), s, rn, re, 0.0, 1.0, mach_dt, 0, false, nullptr,
+                                              nullptr, sy, cy);  // init_step
     sampling_count = 0;
     travel_dist = 0; travel_time = 0; acc = 0;
     n_base = P.n_base0; e_base = P.e_base0;
@@ -1916,7 +1996,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
           imminent = (dn * dn + de * de) < 9000000.0f;
         }
         SHIPSIM_SHIP_CHECK(LPE, SLOTS, 6);  // (its DPP exchanges pair sub-lanes of one ship)
-        control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, P, s, rn, re, -off, sf, mach_dt,
+        control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, P, weather_of(P, lw), s, rn, re, -off, sf, mach_dt,
                                                          (SIMPLE && is_test) ? 1 : 0, imminent,
                                                          (REC && sub == 0) ? T.ship_row(qc, rec_t) : nullptr, fuel, sy,
                                                          cy, los_pre_q, los_pre_e);
@@ -2674,8 +2754,8 @@ __global__ __launch_bounds__(64) void noniw_tick_kernel(NoniwArgs A_arg) {
           s.time = s.time + P.dt;
           s.time = s.time + P.dt;
         } else {
-          control_and_integrate_sc<false, false>(c, P, s, rn, re, -off, sf, 0.0, kFlag, imminent, nullptr, nullptr, sy,
-                                                 cy);
+          control_and_integrate_sc<false, false>(c, P, P, s, rn, re, -off, sf, 0.0, kFlag, imminent, nullptr, nullptr,
+                                                 sy, cy);
         }
       }
     };
@@ -2823,6 +2903,13 @@ struct shipsim_handle {
   int lpe;  // lanes per AST env of the step / stream kernels (lanes_per_env)
   int32_t tail_extra;  // shipsim_set_stream_tail (0: off)
   int32_t* tail_ctr;   // its device counter (one int, zeroed before every stream launch)
+  // shipsim_set_weather: the per-env weather array on the device (kWeatherCols x n_envs, an allocation of its own),
+  // the caller's four arrays as given (4 x n_envs, host: shipsim_get_weather), whether the handle runs on them,
+  // and the lanes per env the handle runs without them (lpe while they are set: the nearest weather kernel's)
+  double* wx_dev;
+  double* wx_host;
+  int wx_on;
+  int lpe_uniform;
   char err[512];
 };
 
@@ -2958,6 +3045,7 @@ static StepArgs step_args_of(const shipsim_handle* h, const float* action, const
   a.action = action; a.active_mask = active; a.max_ticks = max_ticks;
   a.obs_out = obs_out; a.reward_out = reward_out; a.done_out = done_out; a.events_out = events_out;
   a.ticks_out = ticks_out; a.ready_out = ready_out; a.CH = ch;
+  a.weather = h->wx_on ? h->wx_dev : nullptr;
   return a;
 }
 
@@ -3000,6 +3088,40 @@ static void launch_multi(shipsim_handle* h, const float* action, const uint8_t* 
   if (ship_slots(h) == 4) LM(4);
   else LM(8);
 #undef LM
+}
+
+static bool tail_on(const shipsim_handle* h, const void* kern, int blocks);
+
+// Per-env weather (shipsim_set_weather): the ast_step_kernel<.., MODE | kStepWeather, ..> family. Two-ship envs at
+// 8 or 16 lanes per env (weather_lpe), K > 1 at 16 lanes in ship slots; the stream tail as on uniform handles
+// (two-ship envs only).
+static int weather_lpe(const shipsim_handle* h, int lpe) { return (ship_slots(h) == 2 && lpe <= 8) ? 8 : 16; }
+
+template <int CA, int CHAIN>
+static void launch_weather(shipsim_handle* h, const float* action, const uint8_t* active, int32_t max_ticks,
+                           float* obs_out, double* reward_out, uint8_t* done_out, uint32_t* events_out,
+                           int32_t* ticks_out, uint8_t* ready_out, const ChainArgs& ch) {
+  const int slots = ship_slots(h), lpe = weather_lpe(h, h->lpe);
+  const int threads = 64, blocks = step_blocks(h, lpe);
+#define LW(LPE, SL)                                                                                            \
+  do {                                                                                                         \
+    auto kern_ = &ast_step_kernel<true, CA, LPE, false, CHAIN | kStepWeather, SL>;                             \
+    ChainArgs c_ = ch;                                                                                         \
+    if (CHAIN && SL == 2 && tail_on(h, reinterpret_cast<const void*>(kern_), blocks)) {                        \
+      (void)hipMemsetAsync(h->tail_ctr, 0, sizeof(int32_t), h->stream);                                        \
+      c_.tail_ctr = h->tail_ctr;                                                                               \
+      c_.tail_extra = h->tail_extra;                                                                           \
+      c_.tail_waves = blocks;                                                                                  \
+    }                                                                                                          \
+    hipLaunchKernelGGL(kern_, dim3(blocks), dim3(threads), 0, h->stream,                                       \
+                       step_args_of(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,   \
+                                    ticks_out, ready_out, c_));                                                \
+  } while (0)
+  if (slots == 8) LW(16, 8);
+  else if (slots == 4) LW(16, 4);
+  else if (lpe == 8) LW(8, 2);
+  else LW(16, 2);
+#undef LW
 }
 
 extern "C" {
@@ -3312,6 +3434,7 @@ int shipsim_create(const shipsim_config* cfg_in, int32_t n_envs, int32_t n_obs_s
   h->stream = (hipStream_t)stream;
   DeviceGuard g(device);
   h->lpe = cfg->n_ships > 2 ? 16 : lanes_per_env(cfg, n_envs, device);  // K > 1: 16 lanes in ship slots
+  h->lpe_uniform = h->lpe;
   Params& P = h->P;
   memset(&P, 0, sizeof(P));
   P.epw = cfg->envs_per_wave;  // performance knob (0 = full waves; results identical)
@@ -3497,7 +3620,9 @@ int shipsim_destroy(shipsim_handle* h) {
     if (h->fuel_block) (void)hipFree(h->fuel_block);
     if (h->nonfinite_dev) (void)hipFree(h->nonfinite_dev);
     if (h->tail_ctr) (void)hipFree(h->tail_ctr);
+    if (h->wx_dev) (void)hipFree(h->wx_dev);
   }
+  free(h->wx_host);
   delete h;
   return SHIPSIM_OK;
 }
@@ -3519,6 +3644,13 @@ int shipsim_reset(shipsim_handle* h, const uint8_t* env_mask, float* obs_out) {
   DeviceGuard g(h->device);
   int S = h->P.n_envs * h->P.n_ships, threads = 256, blocks = (S + threads - 1) / threads;
   const bool rec = h->T.ship != nullptr;
+  if (h->wx_on) {  // (detailed machinery, no recording: shipsim_set_weather)
+    hipLaunchKernelGGL(reset_wx_kernel, dim3(blocks), dim3(threads), 0, h->stream, h->P, h->S, h->K, env_mask, obs_out,
+                       (const double*)h->wx_dev);
+    HIPCHK(h, hipGetLastError());
+    h->ever_reset = 1;
+    return SHIPSIM_OK;
+  }
 #define RL(D, REC) \
   hipLaunchKernelGGL((reset_kernel<D, REC>), dim3(blocks), dim3(threads), 0, h->stream, h->P, h->S, h->K, h->T, env_mask, obs_out)
   if (h->P.machinery == SHIPSIM_MACH_DETAILED) {
@@ -3555,6 +3687,16 @@ int shipsim_step(shipsim_handle* h, const float* action, const uint8_t* active, 
 #endif
   return fail(h, SHIPSIM_EINVAL, "REGCHECK build");
 #else
+  if (h->wx_on) {
+    if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
+      launch_weather<SHIPSIM_COLLAV_SBMPC, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,
+                                              ticks_out, ready_out, ChainArgs{});
+    else
+      launch_weather<SHIPSIM_COLLAV_NONE, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,
+                                             ticks_out, ready_out, ChainArgs{});
+    HIPCHK(h, hipGetLastError());
+    return SHIPSIM_OK;
+  }
   if (ship_slots(h) > 2) {
     if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
       launch_multi<SHIPSIM_COLLAV_SBMPC, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out,
@@ -3665,6 +3807,16 @@ static int run_chain(shipsim_handle* h, const ChainArgs& ch, int32_t max_ticks, 
   (void)det;
 #endif
 #else
+  if (h->wx_on) {
+    if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
+      launch_weather<SHIPSIM_COLLAV_SBMPC, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
+                                                 ticks_out, nullptr, ch);
+    else
+      launch_weather<SHIPSIM_COLLAV_NONE, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
+                                                ticks_out, nullptr, ch);
+    HIPCHK(h, hipGetLastError());
+    return SHIPSIM_OK;
+  }
   if (ship_slots(h) > 2) {  // K > 1 obstacle ships (collav none / sbmpc: shipsim_create); no launch tail
     if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
       launch_multi<SHIPSIM_COLLAV_SBMPC, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
@@ -3738,6 +3890,7 @@ int shipsim_legacy_step(shipsim_handle* h, int32_t k, double* states_out, uint8_
   if (!h || !h->dev_block || k < 0) return SHIPSIM_EINVAL;
   if (h->P.kind != SHIPSIM_KIND_AST) return fail(h, SHIPSIM_EINVAL, "legacy_step: AST kind only");
   if (h->P.n_ships != 2) return fail(h, SHIPSIM_EINVAL, "legacy_step: the legacy MultiShipEnv has one obstacle ship");
+  if (h->wx_on) return fail(h, SHIPSIM_EINVAL, "legacy_step: per-env weather is set (the legacy kernels run the config's)");
   if (k == 0) return SHIPSIM_OK;
   DeviceGuard g(h->device);
   const int threads = 64, blocks = (2 * h->P.n_envs + threads - 1) / threads;
@@ -3812,6 +3965,9 @@ int shipsim_set_trajectory(shipsim_handle* h, double* ship_rows, double* env_row
     memset(&h->T, 0, sizeof(h->T));
     return SHIPSIM_OK;
   }
+  if (h->wx_on)
+    return fail(h, SHIPSIM_EINVAL, "set_trajectory: per-env weather is set (the recording kernels run the config's "
+                "weather: replay the env on a uniform handle)");
   if (capacity <= 0 || !lengths) return fail(h, SHIPSIM_EINVAL, "set_trajectory: capacity %d / lengths", capacity);
   DeviceGuard g(h->device);
   const size_t fb = (size_t)h->P.n_envs * h->P.n_ships * 3 * sizeof(double);
@@ -3823,6 +3979,76 @@ int shipsim_set_trajectory(shipsim_handle* h, double* ship_rows, double* env_row
   h->T.fuel = (double*)h->fuel_block;
   h->T.len = lengths;
   h->T.cap = capacity;
+  return SHIPSIM_OK;
+}
+
+int shipsim_set_weather(shipsim_handle* h, const double* wind_speed, const double* wind_direction,
+                        const double* current_from_north, const double* current_from_east) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  const int n_null = !wind_speed + !wind_direction + !current_from_north + !current_from_east;
+  if (n_null == 4) {  // back to the config's uniform weather and the uniform kernels
+    h->wx_on = 0;
+    h->lpe = h->lpe_uniform;
+    return SHIPSIM_OK;
+  }
+  if (n_null) return fail(h, SHIPSIM_EINVAL, "set_weather: %d of the four arrays are NULL (all or none)", n_null);
+  const char* why = weather_host::unsupported(h->P.kind, h->P.machinery, h->P.collav, h->T.ship != nullptr);
+  if (why) return fail(h, SHIPSIM_EINVAL, "set_weather: %s", why);
+  const size_t n = (size_t)h->P.n_envs;
+  const int64_t bad = weather_host::check(wind_speed, wind_direction, current_from_north, current_from_east, n);
+  if (bad >= 0)
+    return fail(h, SHIPSIM_EINVAL, "set_weather: env %lld: wind speed %g, wind direction %g, current (%g, %g) "
+                "(finite values and a wind speed >= 0)", (long long)bad, wind_speed[bad], wind_direction[bad],
+                current_from_north[bad], current_from_east[bad]);
+  double* dev_rows = (double*)malloc(sizeof(double) * kWeatherCols * n);
+  double* host = h->wx_host ? h->wx_host : (double*)malloc(sizeof(double) * 4 * n);
+  if (!dev_rows || !host) {
+    free(dev_rows);
+    if (!h->wx_host) free(host);
+    return fail(h, SHIPSIM_ENOMEM, "set_weather: out of host memory");
+  }
+  DeviceGuard g(h->device);
+  if (!h->wx_dev) {
+    hipError_t e = hipMalloc(&h->wx_dev, sizeof(double) * kWeatherCols * n);
+    if (e != hipSuccess) {
+      free(dev_rows);
+      if (!h->wx_host) free(host);
+      h->wx_dev = nullptr;
+      return fail(h, SHIPSIM_EHIP, "hipMalloc(weather): %s", hipGetErrorString(e));
+    }
+  }
+  h->wx_host = host;
+  weather_host::rows(wind_speed, wind_direction, current_from_north, current_from_east, n, dev_rows);
+  // the upload is ordered on the handle's stream behind the launches already queued, and complete on return
+  // (the staging rows are freed here): a change takes effect at the next launch
+  hipError_t e = hipMemcpyAsync(h->wx_dev, dev_rows, sizeof(double) * kWeatherCols * n, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  free(dev_rows);
+  if (e != hipSuccess) {  // the device array is in an unknown state: the handle runs the config's weather
+    h->wx_on = 0;
+    h->lpe = h->lpe_uniform;
+    return fail(h, SHIPSIM_EHIP, "set_weather upload: %s", hipGetErrorString(e));
+  }
+  memcpy(host, wind_speed, sizeof(double) * n);
+  memcpy(host + n, wind_direction, sizeof(double) * n);
+  memcpy(host + 2 * n, current_from_north, sizeof(double) * n);
+  memcpy(host + 3 * n, current_from_east, sizeof(double) * n);
+  h->wx_on = 1;
+  h->lpe = weather_lpe(h, h->lpe_uniform);
+  return SHIPSIM_OK;
+}
+
+int shipsim_get_weather(shipsim_handle* h, double* wind_speed, double* wind_direction, double* current_from_north,
+                        double* current_from_east) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (!wind_speed || !wind_direction || !current_from_north || !current_from_east)
+    return fail(h, SHIPSIM_EINVAL, "get_weather: an output array is NULL");
+  const size_t n = (size_t)h->P.n_envs;
+  double* out[4] = {wind_speed, wind_direction, current_from_north, current_from_east};
+  const double uniform[4] = {h->cfg.wind_speed, h->cfg.wind_direction, h->cfg.current_velocity_component_from_north,
+                             h->cfg.current_velocity_component_from_east};
+  for (int k = 0; k < 4; ++k)
+    for (size_t i = 0; i < n; ++i) out[k][i] = h->wx_on ? h->wx_host[k * n + i] : uniform[k];
   return SHIPSIM_OK;
 }
 

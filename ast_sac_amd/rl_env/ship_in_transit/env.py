@@ -53,7 +53,10 @@ def config_from_args(args, machinery="detailed"):
 
 
 class BatchedMultiShipRLEnv:
-    def __init__(self, args=None, n_envs=1, device=None, machinery="detailed", cfg=None, lanes_per_env=0):
+    def __init__(self, args=None, n_envs=1, device=None, machinery="detailed", cfg=None, lanes_per_env=0,
+                 weather=None):
+        """weather: per-env wind and current, a dict as weather.sample_weather returns (None: the config's, one
+        sea for every env)."""
         self.args = args if args is not None else default_args()
         self.cfg = cfg if cfg is not None else config_from_args(self.args, machinery)
         if lanes_per_env:
@@ -75,6 +78,22 @@ class BatchedMultiShipRLEnv:
                                         self.cfg.ship[1].initial_east_position_m, self.cfg.ship[1].initial_yaw_angle_rad,
                                         0.0, self.cfg.ship[1].initial_forward_speed_m_per_s], dtype=np.float32)
         self._out = None
+        if weather is not None:
+            self.set_weather(weather)
+
+    # -- per-env weather (beyond the reference; weather.py, ShipSim.set_weather) --
+    def set_weather(self, weather):
+        """Per-env weather from a dict of wind_speed, wind_direction [rad], current_north, current_east (arrays of
+        n_envs or scalars; weather.sample_weather draws one); None returns to the config's. Takes effect at the
+        next reset / step and persists across resets."""
+        if weather is None:
+            self.sim.clear_weather()
+        else:
+            self.sim.set_weather(*[weather[k] for k in ShipSim.WEATHER_KEYS])
+
+    def weather(self):
+        """The per-env weather in force (dict of four float64 arrays), or None under the config's."""
+        return self.sim.weather()
 
     # -- reference helpers (env.py:186-196) --
     def do_normalize_action(self, a_real):
@@ -152,13 +171,13 @@ class BatchedMultiShipRLEnv:
     # snapshots (logger.save_itr_params pickles the collectors' env): keep the config, not the device state
     def __getstate__(self):
         return dict(args=self.args, cfg=bytes(self.cfg), n_envs=self.n_envs, device=str(self.device),
-                    n_obs_ships=self.n_obs_ships)
+                    n_obs_ships=self.n_obs_ships, weather=self.weather())
 
     def __setstate__(self, st):
         cfg = abi.Config.from_buffer_copy(st["cfg"])
         if "n_obs_ships" in st:  # (the config carries it too; older snapshots have one obstacle ship)
             cfg.n_ships = 1 + int(st["n_obs_ships"])
-        self.__init__(st["args"], st["n_envs"], device=st["device"], cfg=cfg)
+        self.__init__(st["args"], st["n_envs"], device=st["device"], cfg=cfg, weather=st.get("weather"))
 
 
 class _Int:

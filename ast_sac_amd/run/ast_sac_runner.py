@@ -6,7 +6,8 @@ Same CLI and variant as the reference. Two execution shapes:
   NormalizedBoxEnv, MdpPathCollector(ast_sac_rollout), EnvReplayBuffer, SACTrainer,
   TorchBatchRLAlgorithm — for drop-in use and side-by-side comparison.
 * `--n_envs N` (default 4096): the MI355X shape — N device-resident envs per GPU stepped in
-  slices (`--obs_ships K`, K = 2..4: the multi-obstacle scenario, this shape only), transitions written straight
+  slices (`--obs_ships K`, K = 2..4: the multi-obstacle scenario; `--wind_speed_range LO HI` and its three
+  siblings: every env under its own wind and current; both this shape only), transitions written straight
   into a DeviceReplayBuffer, FusedSACTrainer (HIP-graph
   step) and DeviceBatchRLAlgorithm. Under torch.distributed.run every rank owns N envs. With
   --dp_mode replicated (default) every rank keeps the union of all ranks' transitions (RCCL
@@ -90,9 +91,40 @@ def build_parser():
                         "scenario: shipsim_abi.TRAFFIC_SHIPS[:K-1] sail as ships 2..K (the policy still places ship "
                         "1's waypoints; the ship under test avoids all of them). Needs --machinery detailed, "
                         "--collav_mode sbmpc or none, and --n_envs > 0")
+    # per-env weather (beyond the reference: every env of the batch under its own wind and current)
+    for flag, unit in (("--wind_speed_range", "m/s"), ("--wind_direction_range", "degrees"),
+                       ("--current_speed_range", "m/s"), ("--current_direction_range", "degrees")):
+        p.add_argument(flag, type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                       help=f"every env draws its own value, uniform in [LO, HI] {unit} (rl_env/ship_in_transit/"
+                            "weather.py); not given: the scenario's value. Any of the four needs --machinery detailed, "
+                            "--collav_mode sbmpc or none, and --n_envs > 0")
+    p.add_argument("--weather_seed", type=int, default=0, metavar="S",
+                   help="env i of the whole run (rank r: i = r * n_envs + local index) draws its weather from "
+                        "PCG64(S + i); a separate evaluation shard (--eval_envs) draws with S + 1")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--log_dir", type=str, default=None)
     return p
+
+
+WEATHER_RANGE_FLAGS = (("wind_speed_range", "wind_speed"), ("wind_direction_range", "wind_direction_deg"),
+                       ("current_speed_range", "current_speed"), ("current_direction_range", "current_direction_deg"))
+
+
+def weather_ranges(args):
+    """The ranges given on the command line as sample_weather's keyword arguments, or None when none was."""
+    given = {kw: tuple(getattr(args, flag)) for flag, kw in WEATHER_RANGE_FLAGS
+             if getattr(args, flag, None) is not None}
+    return given or None
+
+
+def weather_for(args, n_envs, first_env=0, evaluation=False, cfg=None):
+    """The per-env weather of a shard of n_envs envs starting at global env first_env (None without range flags)."""
+    ranges = weather_ranges(args)
+    if ranges is None:
+        return None
+    from ..rl_env.ship_in_transit.weather import sample_weather
+    return sample_weather(n_envs, seed=args.weather_seed + (1 if evaluation else 0), first_env=first_env, cfg=cfg,
+                          **ranges)
 
 
 def parse_cli_args(argv=None):
@@ -111,6 +143,23 @@ def parse_cli_args(argv=None):
                     "obstacle ship")
         if args.n_envs <= 0:
             p.error(f"--obs_ships {k} needs --n_envs > 0: the reference single-env graph unpacks [test, obs]")
+    ranges = weather_ranges(args)
+    if ranges is not None:  # what shipsim_set_weather refuses, said here with the reason
+        flag = "--" + next(f for f, kw in WEATHER_RANGE_FLAGS if kw in ranges)
+        if args.machinery != "detailed":
+            p.error(f"{flag} needs --machinery detailed (not --machinery {args.machinery}): the per-env weather "
+                    "kernels are built for the detailed machinery only")
+        if args.collav_mode == "simple":
+            p.error(f"{flag} needs --collav_mode sbmpc or none (not --collav_mode simple): there are no per-env "
+                    "weather kernels for the simple collision avoidance")
+        if args.n_envs <= 0:
+            p.error(f"{flag} needs --n_envs > 0 (not --n_envs {args.n_envs}): the reference single-env graph has "
+                    "one env and one sea")
+        for f, kw in WEATHER_RANGE_FLAGS:
+            if kw in ranges:
+                lo, hi = ranges[kw]
+                if not (np.isfinite(lo) and np.isfinite(hi)) or hi < lo or (kw.endswith("speed") and lo < 0):
+                    p.error(f"--{f} {lo} {hi}: LO <= HI, finite" + (", LO >= 0" if kw.endswith("speed") else ""))
     return args
 
 
@@ -130,6 +179,7 @@ def make_variant(args):
                             action_reg_coeff=args.action_reg_coeff, clip_val=args.clip_val),
         n_envs=args.n_envs, slice_ticks=args.slice_ticks, machinery=args.machinery,
         n_obs_ships=getattr(args, "n_obs_ships", 1),
+        weather=None if weather_ranges(args) is None else dict(weather_ranges(args), seed=args.weather_seed),
         match_update_ratio=args.match_update_ratio, dp_mode=args.dp_mode)
 
 
@@ -191,11 +241,18 @@ def experiment_device(variant, args, device, process_group=None):
     from ..ast_sac.core.device_rl_algorithm import DeviceBatchRLAlgorithm
 
     cfg = config_from_args(args, args.machinery)
-    env = BatchedMultiShipRLEnv(args, args.n_envs, device=device, cfg=cfg)
+    # per-env weather (--*_range): env i of the whole run draws from PCG64(weather_seed + i), so the draw does not
+    # depend on the rank layout; a separate evaluation shard draws its own (weather_seed + 1) over the same ranges,
+    # the default shared env object evaluates on the exploration envs' weather
+    rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
+    env = BatchedMultiShipRLEnv(args, args.n_envs, device=device, cfg=cfg,
+                                weather=weather_for(args, args.n_envs, first_env=rank * args.n_envs, cfg=cfg))
     expl_env = BatchedNormalizedBoxEnv(env, reward_scale=args.reward_scale)
     if args.eval_envs > 0:  # a separate evaluation env shard (not the reference's shape, see below)
         eval_env = BatchedNormalizedBoxEnv(BatchedMultiShipRLEnv(args, args.eval_envs, device=device,
-                                                                 cfg=config_from_args(args, args.machinery)),
+                                                                 cfg=config_from_args(args, args.machinery),
+                                                                 weather=weather_for(args, args.eval_envs,
+                                                                                     evaluation=True, cfg=cfg)),
                                            reward_scale=args.reward_scale)
     else:  # default: one env object under both wrappers, as run/ast-sac_runner.py:113-114 (quirk Q10): the
         # evaluation episodes reset and advance the exploration envs, whose SBMPC memory carries over (Q7)

@@ -7,6 +7,7 @@ __graft_entry__ as g; g.build()"` (hipcc --offload-arch=gfx950).
 import ctypes as C
 import os
 
+import numpy as np
 import torch  # noqa: F401  (loads torch's HIP runtime first; libshipsim binds to the same libamdhip64.so.7)
 
 from . import shipsim_abi as abi
@@ -65,7 +66,9 @@ def load_library(path=LIB_PATH):
                            ("shipsim_diag_lane_faults", [P]),
                            ("shipsim_run_policy", [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, P, C.c_int32,
                                                    C.c_int32, P, P, P, P, P, C.c_int32, P]),
-                           ("shipsim_sbmpc_eval_multi", [C.c_int32, C.c_int32, C.c_double, C.c_double, P, P, P])):
+                           ("shipsim_sbmpc_eval_multi", [C.c_int32, C.c_int32, C.c_double, C.c_double, P, P, P]),
+                           ("shipsim_set_weather", [P, P, P, P, P]),
+                           ("shipsim_get_weather", [P, P, P, P, P])):
         try:
             getattr(L, name).argtypes = argtypes
         except AttributeError:
@@ -88,7 +91,7 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_set_trajectory", "shipsim_sbmpc_eval", "shipsim_legacy_step", "shipsim_run_table",
                     "shipsim_nonfinite_count", "shipsim_lanes_per_env", "shipsim_set_stream",
                     "shipsim_run_policy", "shipsim_diag_lane_faults", "shipsim_set_stream_tail", "shipsim_div_check",
-                    "shipsim_sbmpc_eval_multi")
+                    "shipsim_sbmpc_eval_multi", "shipsim_set_weather", "shipsim_get_weather")
 
 
 def diag_lane_faults():
@@ -142,6 +145,7 @@ class ShipSim:
         self.h = h
         self._stream_ptr = self.stream.cuda_stream
         self.lanes_per_env = int(self.L.shipsim_lanes_per_env(h))
+        self._weather_on = False
 
     def _follow_stream(self):
         """Launch on torch's current stream of the device (e.g. a graph-capturing one): shipsim_set_stream
@@ -296,6 +300,44 @@ class ShipSim:
         self._follow_stream()
         self._check(self.L.shipsim_set_state(self.h, int(field), _ptr(t)), "shipsim_set_state")
         self._keep_set = t
+
+    # -- per-env weather (include/shipsim.h: shipsim_set_weather) --
+    WEATHER_KEYS = ("wind_speed", "wind_direction", "current_north", "current_east")
+
+    def set_weather(self, wind_speed, wind_direction, current_north, current_east):
+        """Per-env wind and current (shipsim_set_weather): four array-likes of n_envs values (m/s, rad, m/s from
+        north, m/s from east), a scalar broadcasts. From the next launch on env i runs under its values, with the
+        results of a uniform handle whose config carries them; they persist across resets. A setup call (it
+        waits for the upload): not during graph capture. lanes_per_env follows what the weather kernels run."""
+        arrs = []
+        for name, x in zip(self.WEATHER_KEYS, (wind_speed, wind_direction, current_north, current_east)):
+            a = np.asarray(x, dtype=np.float64)
+            if a.ndim == 0:
+                a = np.full(self.n_envs, float(a))
+            a = np.ascontiguousarray(a.reshape(-1))
+            if a.size != self.n_envs:
+                raise ShipSimError(f"set_weather: {name} has {a.size} entries, expected {self.n_envs}")
+            arrs.append(a)
+        self._follow_stream()
+        self._check(self.L.shipsim_set_weather(self.h, *[C.c_void_p(a.ctypes.data) for a in arrs]),
+                    "shipsim_set_weather")
+        self._weather_on = True
+        self.lanes_per_env = int(self.L.shipsim_lanes_per_env(self.h))
+
+    def clear_weather(self):
+        """Back to the config's uniform weather and the uniform kernels."""
+        self._check(self.L.shipsim_set_weather(self.h, None, None, None, None), "shipsim_set_weather")
+        self._weather_on = False
+        self.lanes_per_env = int(self.L.shipsim_lanes_per_env(self.h))
+
+    def weather(self):
+        """dict of four float64 arrays of n_envs (WEATHER_KEYS) as set by set_weather; None when uniform."""
+        if not self._weather_on:
+            return None
+        out = [np.empty(self.n_envs, dtype=np.float64) for _ in self.WEATHER_KEYS]
+        self._check(self.L.shipsim_get_weather(self.h, *[C.c_void_p(a.ctypes.data) for a in out]),
+                    "shipsim_get_weather")
+        return dict(zip(self.WEATHER_KEYS, out))
 
     # -- trajectory recording (include/shipsim.h: shipsim_set_trajectory) --
     def set_trajectory(self, capacity, env_rows=True):

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SHIPSIM_ABI_VERSION 11  /* 11: shipsim_run_policy runs K > 1 obstacle ships */
+#define SHIPSIM_ABI_VERSION 12  /* 12: shipsim_set_weather / shipsim_get_weather (per-env wind and current) */
 
 #define SHIPSIM_MAX_ROUTE 16   /* waypoints per ship route (obs ship: 2 + max_sampling_frequency) */
 #define SHIPSIM_MAX_POLYS 16   /* land polygons in the map */
@@ -448,6 +448,31 @@ int shipsim_run_policy(shipsim_handle* h, const float* policy, const float* w2t,
  * faster waves. Used only when every wave of the launch is resident at once (otherwise the launch runs as with 0),
  * and for one obstacle ship per env (the K > 1 streams run as with 0). */
 int shipsim_set_stream_tail(shipsim_handle* h, int32_t extra_ticks);
+
+/* ---- per-env weather (ABI 12) ---------------------------------------------------------------
+ * By default every env of a handle runs the config's weather (wind_speed, wind_direction,
+ * current_velocity_component_from_north / _from_east). shipsim_set_weather gives every env its own: four HOST
+ * arrays of n_envs doubles (m/s, rad, m/s, m/s) — a setup call like the config, not a per-step one. The library
+ * takes sin and cos of the direction on the host (the libm calls shipsim_create makes for the config's direction),
+ * copies the arrays, uploads on the handle's stream and waits for the upload: do not call it during graph capture.
+ * From the next launch on shipsim_reset, shipsim_step, shipsim_run_table and shipsim_run_policy (in-kernel resets
+ * included) run env i under its values, with the results, bit for bit, of a uniform handle whose config carries
+ * them. The values persist across resets until set again.
+ *   - four NULL pointers: back to the config's weather (and the uniform kernels); a mix of NULL and non-NULL,
+ *     a non-finite value or a negative wind speed: SHIPSIM_EINVAL, and nothing changes.
+ *   - AST kind, detailed machinery, collav none / sbmpc, K = 1..4 obstacle ships, no trajectory recording:
+ *     anything else is SHIPSIM_EINVAL with the reason in shipsim_last_error, as are shipsim_set_trajectory and
+ *     shipsim_legacy_step on a handle with per-env weather. (A recorded replay of env i: a uniform handle whose
+ *     config carries env i's values.)
+ *   - the weather kernels exist at 8 and 16 lanes per env (two-ship envs; 16 for K > 1): a handle whose automatic
+ *     or requested lanes_per_env is 2 or 4 runs at 8 while per-env weather is set, and shipsim_lanes_per_env
+ *     reports what runs (results do not depend on it).
+ * shipsim_get_weather fills four host arrays of n_envs doubles with what was set, or with the config's values on
+ * a handle without per-env weather. */
+int shipsim_set_weather(shipsim_handle* h, const double* wind_speed, const double* wind_direction,
+                        const double* current_from_north, const double* current_from_east);
+int shipsim_get_weather(shipsim_handle* h, double* wind_speed, double* wind_direction,
+                        double* current_from_north, double* current_from_east);
 
 /* ---- legacy per-tick MultiShipEnv (rl_env/ship_in_transit/env.py:783-1181) ----
  * AST kind. Each of the k ticks is one MultiShipEnv.step() (:1104-1173) of every env: test_step
