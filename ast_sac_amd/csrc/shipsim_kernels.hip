@@ -22,6 +22,7 @@
 
 #include "shipsim.h"
 #include "shipsim_device.hpp"
+#include "shipsim_launch_host.hpp"   // the list of step kernels and the choice among them
 #include "shipsim_weather_host.hpp"  // shipsim_set_weather's host half
 
 #include "shipsim_diag.hpp"  // diagnostics / ablation hooks (none in the product build)
@@ -3036,9 +3037,70 @@ static int step_blocks(const shipsim_handle* h, int lpe) {
   return (h->P.n_envs + epw - 1) / epw;
 }
 
-static StepArgs step_args_of(const shipsim_handle* h, const float* action, const uint8_t* active, int32_t max_ticks,
-                            float* obs_out, double* reward_out, uint8_t* done_out, uint32_t* events_out,
-                            int32_t* ticks_out, uint8_t* ready_out, const ChainArgs& ch) {
+// The step kernels of the library: shipsim_launch_host.hpp's list, expanded here and nowhere else. A register-usage
+// inspection build (scripts/regcheck.sh N) holds one kernel set only: the other rows are not instantiated and
+// their entries are null.
+constexpr bool step_kernel_built(bool d, int ca, int lpe, bool rec, int mode, int slots) {
+#ifdef SHIPSIM_REGCHECK
+  const bool stream2 = (mode == 1 || mode == 2) && slots == 2;  // a two-ship decision stream, the config's weather
+  return SHIPSIM_REGCHECK == 2 ? stream2 && ca == SHIPSIM_COLLAV_SBMPC && lpe == 8  // the C4 shard's collector
+         : SHIPSIM_REGCHECK == 3                                                    // K > 1: steps and streams
+             ? slots > 2 && mode < kStepWeather && !(mode == 1 && ca == SHIPSIM_COLLAV_NONE)
+             : stream2 && d && ca != SHIPSIM_COLLAV_SIMPLE && lpe == 16;            // the headline streams
+#else
+  return true;
+#endif
+}
+typedef void (*StepKernel)(const StepArgs);
+template <bool BUILT, bool D, int CA, int LPE, bool REC, int MODE, int SLOTS>
+constexpr StepKernel step_kernel_if() {
+  if constexpr (BUILT) return &ast_step_kernel<D, CA, LPE, REC, MODE, SLOTS>;
+  else return nullptr;
+}
+static const struct { int key; StepKernel kern; } kStepKernels[] = {
+#define ROW(D, CA, LPE, REC, MODE, SLOTS)          \
+  {launch_host::step_key(D, CA, LPE, REC, MODE, SLOTS), \
+   step_kernel_if<step_kernel_built(D, CA, LPE, REC, MODE, SLOTS), D, CA, LPE, REC, MODE, SLOTS>()},
+    SHIPSIM_STEP_KERNELS(ROW)
+#undef ROW
+};
+static_assert(launch_host::kWeatherMode == kStepWeather, "MODE's weather bit");
+
+// what launch_host::select says of this handle at an entry point
+static launch_host::Selection selection(const shipsim_handle* h, launch_host::Entry entry) {
+  return launch_host::select(h->P.machinery, h->P.collav, h->P.n_ships, h->lpe_uniform, h->T.ship != nullptr,
+                             h->wx_on != 0, entry);
+}
+
+// the launch tail is used when it is on and every wave of the launch is resident at once (one 64-thread block per
+// wave): a wave that is not resident yet would only start after the resident ones ran their whole extension
+static bool tail_on(const shipsim_handle* h, const void* kern, int blocks) {
+  if (h->tail_extra <= 0 || !h->tail_ctr) return false;
+  int per_cu = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0) != hipSuccess) return false;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) return false;
+  return (int64_t)blocks <= (int64_t)per_cu * cus;
+}
+
+// Every launch of a step kernel: shipsim_step, shipsim_run_table and shipsim_run_policy.
+static int launch_ast(shipsim_handle* h, launch_host::Entry entry, const float* action, const uint8_t* active,
+                      int32_t max_ticks, float* obs_out, double* reward_out, uint8_t* done_out, uint32_t* events_out,
+                      int32_t* ticks_out, uint8_t* ready_out, ChainArgs ch) {
+  static const char* const kEntryName[] = {"step", "run_table", "run_policy"};
+  const launch_host::Selection sel = selection(h, entry);
+  if (sel.why) return fail(h, SHIPSIM_EINVAL, "%s: %s", kEntryName[entry], sel.why);
+  StepKernel kern = nullptr;
+  for (const auto& row : kStepKernels)
+    if (row.key == sel.key) kern = row.kern;
+  if (!kern) return fail(h, SHIPSIM_EINVAL, "REGCHECK build");  // (every selection is a row: test_launch_host_cpu.py)
+  DeviceGuard g(h->device);
+  const int blocks = step_blocks(h, sel.lpe);
+  if (sel.tail && tail_on(h, reinterpret_cast<const void*>(kern), blocks)) {
+    (void)hipMemsetAsync(h->tail_ctr, 0, sizeof(int32_t), h->stream);
+    ch.tail_ctr = h->tail_ctr;
+    ch.tail_extra = h->tail_extra;
+    ch.tail_waves = blocks;
+  }
   StepArgs a;
   memset(&a, 0, sizeof(a));
   a.P = h->P; a.S = h->S; a.K = h->K; a.T = h->T;
@@ -3046,82 +3108,9 @@ static StepArgs step_args_of(const shipsim_handle* h, const float* action, const
   a.obs_out = obs_out; a.reward_out = reward_out; a.done_out = done_out; a.events_out = events_out;
   a.ticks_out = ticks_out; a.ready_out = ready_out; a.CH = ch;
   a.weather = h->wx_on ? h->wx_dev : nullptr;
-  return a;
-}
-
-template <bool D, int CA>
-static void launch_step(shipsim_handle* h, int lpe, const float* action, const uint8_t* active, int32_t max_ticks,
-                        float* obs_out, double* reward_out, uint8_t* done_out, uint32_t* events_out,
-                        int32_t* ticks_out, uint8_t* ready_out) {
-  const int threads = 64;
-  if (h->T.ship) lpe = 16;  // recording kernels are built for the default layout only
-  const int blocks = step_blocks(h, lpe);
-#define L(LPE, REC)                                                                                              \
-  hipLaunchKernelGGL((ast_step_kernel<D, CA, LPE, REC>), dim3(blocks), dim3(threads), 0, h->stream,            \
-                     step_args_of(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out, ticks_out, \
-                                  ready_out, ChainArgs{}))
-  if (h->T.ship) {
-    L(16, true);
-    return;
-  }
-  switch (lpe) {
-    case 2: L(2, false); break;
-    case 4: L(4, false); break;
-    case 8: L(8, false); break;
-    default: L(16, false); break;
-  }
-#undef L
-}
-
-// K > 1 obstacle ships (detailed machinery, collav none / sbmpc): 16 lanes per env in 4 or 8 ship slots
-static int ship_slots(const shipsim_handle* h) { return h->P.n_ships <= 2 ? 2 : (h->P.n_ships <= 4 ? 4 : 8); }
-
-template <int CA, int CHAIN>
-static void launch_multi(shipsim_handle* h, const float* action, const uint8_t* active, int32_t max_ticks,
-                         float* obs_out, double* reward_out, uint8_t* done_out, uint32_t* events_out,
-                         int32_t* ticks_out, uint8_t* ready_out, const ChainArgs& ch) {
-  const int threads = 64, blocks = step_blocks(h, 16);
-#define LM(SL)                                                                                                         \
-  hipLaunchKernelGGL((ast_step_kernel<true, CA, 16, false, CHAIN, SL>), dim3(blocks), dim3(threads), 0, h->stream,  \
-                     step_args_of(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out, ticks_out, \
-                                  ready_out, ch))
-  if (ship_slots(h) == 4) LM(4);
-  else LM(8);
-#undef LM
-}
-
-static bool tail_on(const shipsim_handle* h, const void* kern, int blocks);
-
-// Per-env weather (shipsim_set_weather): the ast_step_kernel<.., MODE | kStepWeather, ..> family. Two-ship envs at
-// 8 or 16 lanes per env (weather_lpe), K > 1 at 16 lanes in ship slots; the stream tail as on uniform handles
-// (two-ship envs only).
-static int weather_lpe(const shipsim_handle* h, int lpe) { return (ship_slots(h) == 2 && lpe <= 8) ? 8 : 16; }
-
-template <int CA, int CHAIN>
-static void launch_weather(shipsim_handle* h, const float* action, const uint8_t* active, int32_t max_ticks,
-                           float* obs_out, double* reward_out, uint8_t* done_out, uint32_t* events_out,
-                           int32_t* ticks_out, uint8_t* ready_out, const ChainArgs& ch) {
-  const int slots = ship_slots(h), lpe = weather_lpe(h, h->lpe);
-  const int threads = 64, blocks = step_blocks(h, lpe);
-#define LW(LPE, SL)                                                                                            \
-  do {                                                                                                         \
-    auto kern_ = &ast_step_kernel<true, CA, LPE, false, CHAIN | kStepWeather, SL>;                             \
-    ChainArgs c_ = ch;                                                                                         \
-    if (CHAIN && SL == 2 && tail_on(h, reinterpret_cast<const void*>(kern_), blocks)) {                        \
-      (void)hipMemsetAsync(h->tail_ctr, 0, sizeof(int32_t), h->stream);                                        \
-      c_.tail_ctr = h->tail_ctr;                                                                               \
-      c_.tail_extra = h->tail_extra;                                                                           \
-      c_.tail_waves = blocks;                                                                                  \
-    }                                                                                                          \
-    hipLaunchKernelGGL(kern_, dim3(blocks), dim3(threads), 0, h->stream,                                       \
-                       step_args_of(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,   \
-                                    ticks_out, ready_out, c_));                                                \
-  } while (0)
-  if (slots == 8) LW(16, 8);
-  else if (slots == 4) LW(16, 4);
-  else if (lpe == 8) LW(8, 2);
-  else LW(16, 2);
-#undef LW
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return SHIPSIM_OK;
 }
 
 extern "C" {
@@ -3382,8 +3371,8 @@ static int validate(const shipsim_config* cfg, char* err, size_t n) {
     ns = cfg->n_ships;
     if (ns < 2 || ns > SHIPSIM_MAX_SHIPS)
       return snprintf(err, n, "n_ships %d: 1 ship under test + 1..%d obstacle ships", ns, SHIPSIM_MAX_OBS), 1;
-    if (ns > 2 && (cfg->machinery != SHIPSIM_MACH_DETAILED || cfg->collav == SHIPSIM_COLLAV_SIMPLE))
-      return snprintf(err, n, "%d obstacle ships: detailed machinery and collav none / sbmpc only", ns - 1), 1;
+    const char* why = launch_host::select(cfg->machinery, cfg->collav, ns, 16, false, false, launch_host::kStep).why;
+    if (why) return snprintf(err, n, "%d obstacle ships: %s", ns - 1, why), 1;
   }
   if (cfg->n_ships != ns) return snprintf(err, n, "n_ships %d != %d for kind %d", cfg->n_ships, ns, cfg->kind), 1;
   if (!(cfg->time_step > 0)) return snprintf(err, n, "time_step must be > 0"), 1;
@@ -3433,7 +3422,8 @@ int shipsim_create(const shipsim_config* cfg_in, int32_t n_envs, int32_t n_obs_s
   h->device = device;
   h->stream = (hipStream_t)stream;
   DeviceGuard g(device);
-  h->lpe = cfg->n_ships > 2 ? 16 : lanes_per_env(cfg, n_envs, device);  // K > 1: 16 lanes in ship slots
+  h->lpe = launch_host::select(cfg->machinery, cfg->collav, cfg->n_ships, lanes_per_env(cfg, n_envs, device), false,
+                               false, launch_host::kStep).lpe;
   h->lpe_uniform = h->lpe;
   Params& P = h->P;
   memset(&P, 0, sizeof(P));
@@ -3643,22 +3633,14 @@ int shipsim_reset(shipsim_handle* h, const uint8_t* env_mask, float* obs_out) {
     return fail(h, SHIPSIM_EINVAL, "reset: kind %d not supported on device", h->P.kind);
   DeviceGuard g(h->device);
   int S = h->P.n_envs * h->P.n_ships, threads = 256, blocks = (S + threads - 1) / threads;
-  const bool rec = h->T.ship != nullptr;
-  if (h->wx_on) {  // (detailed machinery, no recording: shipsim_set_weather)
+  static const decltype(&reset_kernel<true, true>) kReset[2][2] = {  // [detailed machinery][recording]
+      {reset_kernel<false, false>, reset_kernel<false, true>}, {reset_kernel<true, false>, reset_kernel<true, true>}};
+  if (h->wx_on)  // (detailed machinery, no recording: shipsim_set_weather)
     hipLaunchKernelGGL(reset_wx_kernel, dim3(blocks), dim3(threads), 0, h->stream, h->P, h->S, h->K, env_mask, obs_out,
                        (const double*)h->wx_dev);
-    HIPCHK(h, hipGetLastError());
-    h->ever_reset = 1;
-    return SHIPSIM_OK;
-  }
-#define RL(D, REC) \
-  hipLaunchKernelGGL((reset_kernel<D, REC>), dim3(blocks), dim3(threads), 0, h->stream, h->P, h->S, h->K, h->T, env_mask, obs_out)
-  if (h->P.machinery == SHIPSIM_MACH_DETAILED) {
-    if (rec) RL(true, true); else RL(true, false);
-  } else {
-    if (rec) RL(false, true); else RL(false, false);
-  }
-#undef RL
+  else
+    hipLaunchKernelGGL(kReset[h->P.machinery == SHIPSIM_MACH_DETAILED][h->T.ship != nullptr], dim3(blocks),
+                       dim3(threads), 0, h->stream, h->P, h->S, h->K, h->T, env_mask, obs_out);
   HIPCHK(h, hipGetLastError());
   h->ever_reset = 1;
   return SHIPSIM_OK;
@@ -3671,51 +3653,8 @@ int shipsim_step(shipsim_handle* h, const float* action, const uint8_t* active, 
   if (h->P.kind != SHIPSIM_KIND_AST) return fail(h, SHIPSIM_EINVAL, "step: only SHIPSIM_KIND_AST has decision steps");
   if (!action) return fail(h, SHIPSIM_EINVAL, "step: action is NULL");
   if (!h->ever_reset) return fail(h, SHIPSIM_ESTATE, "step before reset");
-  DeviceGuard g(h->device);
-  const int lpe = h->lpe;
-  const bool det = h->P.machinery == SHIPSIM_MACH_DETAILED;
-#define LAUNCH(D, CA) launch_step<D, CA>(h, lpe, action, active, max_ticks, obs_out, reward_out, done_out, events_out, ticks_out, ready_out)
-#ifdef SHIPSIM_REGCHECK  // register-usage inspection builds (scripts/regcheck.sh): headline kernels only
-  (void)lpe; (void)det;
-#if SHIPSIM_REGCHECK == 3  // the multi-obstacle (K > 1) kernels
-  if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
-    launch_multi<SHIPSIM_COLLAV_SBMPC, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,
-                                          ticks_out, ready_out, ChainArgs{});
-  else
-    launch_multi<SHIPSIM_COLLAV_NONE, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,
-                                         ticks_out, ready_out, ChainArgs{});
-#endif
-  return fail(h, SHIPSIM_EINVAL, "REGCHECK build");
-#else
-  if (h->wx_on) {
-    if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
-      launch_weather<SHIPSIM_COLLAV_SBMPC, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,
-                                              ticks_out, ready_out, ChainArgs{});
-    else
-      launch_weather<SHIPSIM_COLLAV_NONE, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out, events_out,
-                                             ticks_out, ready_out, ChainArgs{});
-    HIPCHK(h, hipGetLastError());
-    return SHIPSIM_OK;
-  }
-  if (ship_slots(h) > 2) {
-    if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
-      launch_multi<SHIPSIM_COLLAV_SBMPC, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out,
-                                                events_out, ticks_out, ready_out, ChainArgs{});
-    else
-      launch_multi<SHIPSIM_COLLAV_NONE, 0>(h, action, active, max_ticks, obs_out, reward_out, done_out,
-                                               events_out, ticks_out, ready_out, ChainArgs{});
-    HIPCHK(h, hipGetLastError());
-    return SHIPSIM_OK;
-  }
-  switch (h->P.collav) {
-    case SHIPSIM_COLLAV_NONE: if (det) LAUNCH(true, 0); else LAUNCH(false, 0); break;
-    case SHIPSIM_COLLAV_SIMPLE: if (det) LAUNCH(true, 1); else LAUNCH(false, 1); break;
-    default: if (det) LAUNCH(true, 2); else LAUNCH(false, 2); break;
-  }
-#endif
-#undef LAUNCH
-  HIPCHK(h, hipGetLastError());
-  return SHIPSIM_OK;
+  return launch_ast(h, launch_host::kStep, action, active, max_ticks, obs_out, reward_out, done_out, events_out,
+                    ticks_out, ready_out, ChainArgs{});
 }
 
 int shipsim_tick(shipsim_handle* h, int32_t k, uint32_t* events_out) {
@@ -3728,12 +3667,11 @@ int shipsim_tick(shipsim_handle* h, int32_t k, uint32_t* events_out) {
     if (h->P.machinery != SHIPSIM_MACH_SIMPLIFIED)
       return fail(h, SHIPSIM_EINVAL, "tick: KIND_NONIW runs the simplified machinery (run_colav SimpleShipModel)");
     const int blocks = (2 * h->P.n_envs + 63) / 64;
-#define NT(CA) \
-  hipLaunchKernelGGL(noniw_tick_kernel<CA>, dim3(blocks), dim3(64), 0, h->stream, NoniwArgs{h->P, h->S, h->K, k, events_out})
-    if (h->P.collav == SHIPSIM_COLLAV_SBMPC) NT(SHIPSIM_COLLAV_SBMPC);
-    else if (h->P.collav == SHIPSIM_COLLAV_SIMPLE) NT(SHIPSIM_COLLAV_SIMPLE);
-    else NT(SHIPSIM_COLLAV_NONE);
-#undef NT
+    static const decltype(&noniw_tick_kernel<0>) kNoniw[3] = {  // [collav]
+        noniw_tick_kernel<SHIPSIM_COLLAV_NONE>, noniw_tick_kernel<SHIPSIM_COLLAV_SIMPLE>,
+        noniw_tick_kernel<SHIPSIM_COLLAV_SBMPC>};
+    hipLaunchKernelGGL(kNoniw[h->P.collav], dim3(blocks), dim3(64), 0, h->stream,
+                       NoniwArgs{h->P, h->S, h->K, k, events_out});
     HIPCHK(h, hipGetLastError());
     return SHIPSIM_OK;
   }
@@ -3750,93 +3688,10 @@ int shipsim_tick(shipsim_handle* h, int32_t k, uint32_t* events_out) {
 
 }  // extern "C"
 
-// the launch tail is used when it is on and every wave of the launch is resident at once (one 64-thread block per
-// wave): a wave that is not resident yet would only start after the resident ones ran their whole extension
-static bool tail_on(const shipsim_handle* h, const void* kern, int blocks) {
-  if (h->tail_extra <= 0 || !h->tail_ctr) return false;
-  int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0) != hipSuccess) return false;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) return false;
-  return (int64_t)blocks <= (int64_t)per_cu * cus;
-}
-
-// the decision-stream launch shared by shipsim_run_table (MODE 1) and shipsim_run_policy (MODE 2)
-template <int MODE>
-static int run_chain(shipsim_handle* h, const ChainArgs& ch, int32_t max_ticks, int32_t* ticks_out) {
-  DeviceGuard g(h->device);
-  // lanes per env: 16 (default) or 8 / 4 (more envs per wave when the handle holds more envs than
-  // the chip has SIMD slots at 16; identical results)
-  const int lpe = (h->lpe == 8 || h->lpe == 4) ? h->lpe : (h->lpe == 2 ? 4 : 16);
-  const int threads = 64, blocks = step_blocks(h, lpe);
-#define CHAINED_L(D, CA, LPE)                                                                                      \
-  do {                                                                                                             \
-    const void* kern_ = reinterpret_cast<const void*>(&ast_step_kernel<D, CA, LPE, false, MODE>);                 \
-    ChainArgs c_ = ch;                                                                                             \
-    if (tail_on(h, kern_, blocks)) {                                                                               \
-      (void)hipMemsetAsync(h->tail_ctr, 0, sizeof(int32_t), h->stream);                                            \
-      c_.tail_ctr = h->tail_ctr;                                                                                   \
-      c_.tail_extra = h->tail_extra;                                                                               \
-      c_.tail_waves = blocks;                                                                                      \
-    }                                                                                                              \
-    hipLaunchKernelGGL((ast_step_kernel<D, CA, LPE, false, MODE>), dim3(blocks), dim3(threads), 0, h->stream,    \
-                       step_args_of(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr, ticks_out, \
-                                    nullptr, c_));                                                                 \
-  } while (0)
-#define CHAINED(D, CA)                              \
-  do {                                              \
-    if (lpe == 8) CHAINED_L(D, CA, 8);              \
-    else if (lpe == 4) CHAINED_L(D, CA, 4);         \
-    else CHAINED_L(D, CA, 16);                      \
-  } while (0)
-  const bool det = h->P.machinery == SHIPSIM_MACH_DETAILED;
-#ifdef SHIPSIM_REGCHECK
-#if SHIPSIM_REGCHECK == 2  // the LPE-8 stream kernels (the C4 shard's collector)
-  if (det) CHAINED_L(true, SHIPSIM_COLLAV_SBMPC, 8);
-  else CHAINED_L(false, SHIPSIM_COLLAV_SBMPC, 8);
-#elif SHIPSIM_REGCHECK == 3  // the multi-obstacle decision streams (table: sbmpc; policy: sbmpc and none)
-  (void)det;
-  if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
-    launch_multi<SHIPSIM_COLLAV_SBMPC, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
-                                             ticks_out, nullptr, ch);
-  else if (MODE == 2)
-    launch_multi<SHIPSIM_COLLAV_NONE, 2>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr, ticks_out,
-                                         nullptr, ch);
-#else
-  if (h->P.collav == SHIPSIM_COLLAV_SBMPC) CHAINED_L(true, SHIPSIM_COLLAV_SBMPC, 16);
-  else CHAINED_L(true, SHIPSIM_COLLAV_NONE, 16);
-  (void)det;
-#endif
-#else
-  if (h->wx_on) {
-    if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
-      launch_weather<SHIPSIM_COLLAV_SBMPC, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
-                                                 ticks_out, nullptr, ch);
-    else
-      launch_weather<SHIPSIM_COLLAV_NONE, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
-                                                ticks_out, nullptr, ch);
-    HIPCHK(h, hipGetLastError());
-    return SHIPSIM_OK;
-  }
-  if (ship_slots(h) > 2) {  // K > 1 obstacle ships (collav none / sbmpc: shipsim_create); no launch tail
-    if (h->P.collav == SHIPSIM_COLLAV_SBMPC)
-      launch_multi<SHIPSIM_COLLAV_SBMPC, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
-                                               ticks_out, nullptr, ch);
-    else
-      launch_multi<SHIPSIM_COLLAV_NONE, MODE>(h, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr,
-                                              ticks_out, nullptr, ch);
-    HIPCHK(h, hipGetLastError());
-    return SHIPSIM_OK;
-  }
-  switch (h->P.collav) {
-    case SHIPSIM_COLLAV_SBMPC: if (det) CHAINED(true, SHIPSIM_COLLAV_SBMPC); else CHAINED(false, SHIPSIM_COLLAV_SBMPC); break;
-    case SHIPSIM_COLLAV_SIMPLE: if (det) CHAINED(true, SHIPSIM_COLLAV_SIMPLE); else CHAINED(false, SHIPSIM_COLLAV_SIMPLE); break;
-    default: if (det) CHAINED(true, SHIPSIM_COLLAV_NONE); else CHAINED(false, SHIPSIM_COLLAV_NONE); break;
-  }
-#endif
-#undef CHAINED
-#undef CHAINED_L
-  HIPCHK(h, hipGetLastError());
-  return SHIPSIM_OK;
+// the decision-stream launch shared by shipsim_run_table and shipsim_run_policy
+static int run_chain(shipsim_handle* h, launch_host::Entry entry, const ChainArgs& ch, int32_t max_ticks,
+                     int32_t* ticks_out) {
+  return launch_ast(h, entry, nullptr, nullptr, max_ticks, nullptr, nullptr, nullptr, nullptr, ticks_out, nullptr, ch);
 }
 
 extern "C" {
@@ -3848,11 +3703,10 @@ int shipsim_run_table(shipsim_handle* h, const float* table, int32_t n_eps, int3
       (log && (!log_len || log_cap < 1)))
     return SHIPSIM_EINVAL;
   if (h->P.kind != SHIPSIM_KIND_AST) return fail(h, SHIPSIM_EINVAL, "run_table: AST kind only");
-  if (h->T.ship) return fail(h, SHIPSIM_EINVAL, "run_table: trajectory recording is on (use shipsim_step)");
   ChainArgs ch = {};
   ch.table = table; ch.n_eps = n_eps; ch.n_dec = n_dec; ch.ep_idx = ep_idx; ch.dec_idx = dec_idx;
   ch.decisions = decisions_out; ch.log = log; ch.log_len = log_len; ch.log_cap = log_cap;
-  return run_chain<1>(h, ch, max_ticks, ticks_out);
+  return run_chain(h, launch_host::kTable, ch, max_ticks, ticks_out);
 }
 
 int shipsim_run_policy(shipsim_handle* h, const float* policy, const float* w2t, int32_t obs_dim, int32_t hidden,
@@ -3863,7 +3717,8 @@ int shipsim_run_policy(shipsim_handle* h, const float* policy, const float* w2t,
       (log && (!log_len || log_cap < 1)) || (!deterministic && !counter))
     return SHIPSIM_EINVAL;
   if (h->P.kind != SHIPSIM_KIND_AST) return fail(h, SHIPSIM_EINVAL, "run_policy: AST kind only");
-  if (h->T.ship) return fail(h, SHIPSIM_EINVAL, "run_policy: trajectory recording is on (use shipsim_step)");
+  if (const char* why = selection(h, launch_host::kPolicy).why)  // (before the policy's shape, as ever)
+    return fail(h, SHIPSIM_EINVAL, "run_policy: %s", why);
   if (obs_dim != 8) return fail(h, SHIPSIM_EINVAL, "run_policy: observation dim %d (the AST observation has 8)", obs_dim);
   if (hidden < 64 || hidden > kPolMaxHidden || hidden % 64)
     return fail(h, SHIPSIM_EINVAL, "run_policy: hidden %d (a multiple of 64 up to 512)", hidden);
@@ -3873,7 +3728,7 @@ int shipsim_run_policy(shipsim_handle* h, const float* policy, const float* w2t,
   ch.log_stop = log ? 1 : 0;
   ch.policy = policy; ch.w2t = w2t; ch.pol_obs = obs_dim; ch.pol_hidden = hidden; ch.pol_det = deterministic ? 1 : 0;
   ch.pol_seed = seed; ch.pol_counter = counter;
-  return run_chain<2>(h, ch, max_ticks, ticks_out);
+  return run_chain(h, launch_host::kPolicy, ch, max_ticks, ticks_out);
 }
 
 int shipsim_set_stream_tail(shipsim_handle* h, int32_t extra_ticks) {
@@ -3895,20 +3750,16 @@ int shipsim_legacy_step(shipsim_handle* h, int32_t k, double* states_out, uint8_
   DeviceGuard g(h->device);
   const int threads = 64, blocks = (2 * h->P.n_envs + threads - 1) / threads;
   const LegacyArgs la{h->P, h->S, h->K, k, states_out, done_out, status_out};
-#define LEGACY(D, CA) hipLaunchKernelGGL((legacy_step_kernel<D, CA>), dim3(blocks), dim3(threads), 0, h->stream, la)
-  const bool det = h->P.machinery == SHIPSIM_MACH_DETAILED;
-#ifdef SHIPSIM_REGCHECK
-  (void)det;
+#ifdef SHIPSIM_REGCHECK  // (register-usage inspection builds hold no legacy kernels)
   return fail(h, SHIPSIM_EINVAL, "REGCHECK build");
 #else
-  switch (h->P.collav) {
-    case SHIPSIM_COLLAV_SBMPC: if (det) LEGACY(true, SHIPSIM_COLLAV_SBMPC); else LEGACY(false, SHIPSIM_COLLAV_SBMPC); break;
-    case SHIPSIM_COLLAV_SIMPLE: if (det) LEGACY(true, SHIPSIM_COLLAV_SIMPLE); else LEGACY(false, SHIPSIM_COLLAV_SIMPLE); break;
-    default: if (det) LEGACY(true, SHIPSIM_COLLAV_NONE); else LEGACY(false, SHIPSIM_COLLAV_NONE); break;
-  }
-#endif
+#define LEGACY(D) {legacy_step_kernel<D, 0>, legacy_step_kernel<D, 1>, legacy_step_kernel<D, 2>}
+  static const decltype(&legacy_step_kernel<true, 0>) kLegacy[2][3] = {LEGACY(false), LEGACY(true)};  // [detailed][collav]
 #undef LEGACY
+  hipLaunchKernelGGL(kLegacy[h->P.machinery == SHIPSIM_MACH_DETAILED][h->P.collav], dim3(blocks), dim3(threads), 0,
+                     h->stream, la);
   HIPCHK(h, hipGetLastError());
+#endif
   return SHIPSIM_OK;
 }
 
@@ -3992,7 +3843,7 @@ int shipsim_set_weather(shipsim_handle* h, const double* wind_speed, const doubl
     return SHIPSIM_OK;
   }
   if (n_null) return fail(h, SHIPSIM_EINVAL, "set_weather: %d of the four arrays are NULL (all or none)", n_null);
-  const char* why = weather_host::unsupported(h->P.kind, h->P.machinery, h->P.collav, h->T.ship != nullptr);
+  const char* why = weather_host::unsupported(h->P.kind, h->P.machinery, h->P.collav, h->T.ship != nullptr, h->P.n_ships);
   if (why) return fail(h, SHIPSIM_EINVAL, "set_weather: %s", why);
   const size_t n = (size_t)h->P.n_envs;
   const int64_t bad = weather_host::check(wind_speed, wind_direction, current_from_north, current_from_east, n);
@@ -4034,7 +3885,7 @@ int shipsim_set_weather(shipsim_handle* h, const double* wind_speed, const doubl
   memcpy(host + 2 * n, current_from_north, sizeof(double) * n);
   memcpy(host + 3 * n, current_from_east, sizeof(double) * n);
   h->wx_on = 1;
-  h->lpe = weather_lpe(h, h->lpe_uniform);
+  h->lpe = selection(h, launch_host::kStep).lpe;
   return SHIPSIM_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "shipsim.h"
+#include "shipsim_launch_host.hpp"
 
 namespace weather_host {
 
@@ -15,14 +16,10 @@ namespace weather_host {
 constexpr int kCols = 5;
 constexpr int kWindSpeed = 0, kWindSin = 1, kWindCos = 2, kCurrentN = 3, kCurrentE = 4;
 
-// why a handle of this kind cannot run per-env weather (NULL: it can)
-inline const char* unsupported(int kind, int machinery, int collav, bool recording) {
+// why a handle of this kind cannot run per-env weather (NULL: it can); the kernels' side of it is launch_host::select
+inline const char* unsupported(int kind, int machinery, int collav, bool recording, int n_ships = 2) {
   if (kind != SHIPSIM_KIND_AST) return "SHIPSIM_KIND_AST only (the SINGLE and NONIW kernels run the config's weather)";
-  if (machinery != SHIPSIM_MACH_DETAILED)
-    return "detailed machinery only (no weather kernels for the simplified machinery)";
-  if (collav == SHIPSIM_COLLAV_SIMPLE) return "collav none / sbmpc only (no weather kernels for collav simple)";
-  if (recording) return "trajectory recording is on (the recording kernels run the config's weather)";
-  return nullptr;
+  return launch_host::select(machinery, collav, n_ships, 16, recording, true, launch_host::kStep).why;
 }
 
 // the first env whose values are refused — a non-finite value or a negative wind speed — or -1
