@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "shipsim.h"
 #include "shipsim_diag.hpp"
 
@@ -103,6 +105,80 @@ struct LaneWeather {
 // the device array behind it: kWeatherCols columns of n_envs doubles each
 constexpr int kWeatherCols = 5;
 enum { WX_WIND_SPEED = 0, WX_WIND_SIN = 1, WX_WIND_COS = 2, WX_VC_N = 3, WX_VC_E = 4 };
+
+// ---------------------------------------------------------------------------------------------
+// launch constants in accumulator registers (the two-slot LPE-16 decision streams)
+// ---------------------------------------------------------------------------------------------
+// A number the lane keeps for the whole launch in the accumulator half of its register file (one wave per SIMD:
+// the step kernels leave most of that half unused), written once at the kernel's entry and read back where it is
+// used with one v_accvgpr_read_b32 per dword: a VALU move, no memory counter, no wait. The read is volatile, so
+// it stays at its use inside the tick loop (not hoisted into a VGPR held across the loop, not merged across
+// ticks). Numbers only: no address and no lane mask is ever kept this way.
+struct AccI {
+  int32_t a;
+  __device__ __forceinline__ void set(int32_t x) { asm("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(x)); }
+  __device__ __forceinline__ operator int32_t() const {
+    int32_t x;
+    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(x) : "a"(a));
+    return x;
+  }
+};
+struct AccD {
+  AccI lo, hi;
+  __device__ __forceinline__ void set(double x) { lo.set(__double2loint(x)); hi.set(__double2hiint(x)); }
+  __device__ __forceinline__ operator double() const {
+    const int32_t h = hi, l = lo;
+    return __hiloint2double(h, l);
+  }
+};
+
+// The arithmetic fields of Params and of the map grid (ConstBuf) a tick or a decision's start reads, under their
+// own names. Wave-uniform values, each lane holding its copy.
+#define SHIPSIM_TICK_PARAMS_D(X)                                                                                    \
+  X(dt) X(sim_time) X(vc_n) X(vc_e) X(wind_speed) X(wind_sin) X(wind_cos) X(roa2) X(sbmpc_dt) X(AB_seg)             \
+  X(min_north) X(max_north) X(min_east) X(max_east)
+#define SHIPSIM_TICK_PARAMS_I(X) X(max_sampling) X(sbmpc_nsamp)
+#define SHIPSIM_TICK_GRID_D(X) X(gx0) X(gy0) X(ginv)
+#define SHIPSIM_TICK_GRID_I(X) X(gnx) X(gny)
+struct TickConstRegs {
+#define X(f) AccD f;
+  SHIPSIM_TICK_PARAMS_D(X) SHIPSIM_TICK_GRID_D(X)
+#undef X
+#define X(f) AccI f;
+  SHIPSIM_TICK_PARAMS_I(X) SHIPSIM_TICK_GRID_I(X)
+#undef X
+  template <class G>
+  __device__ __forceinline__ void load(const Params& P, const G& K) {
+#define X(f) f.set(P.f);
+    SHIPSIM_TICK_PARAMS_D(X) SHIPSIM_TICK_PARAMS_I(X)
+#undef X
+#define X(f) f.set(K.f);
+    SHIPSIM_TICK_GRID_D(X) SHIPSIM_TICK_GRID_I(X)
+#undef X
+  }
+};
+
+// the step length alone, under Params' name: what the control chain and the integrator read of Params, for a
+// caller that holds dt as a value
+struct TickStep {
+  double dt;
+};
+
+// grid cell of (north, east), or -1 outside the grid / no grid / non-finite position. G: the grid's origin, cell
+// size and extent, ConstBuf's fields or their register copies.
+template <class G>
+__device__ __forceinline__ int grid_cell(const G& g, double n, double e) {
+  const double fx = floor((e - g.gx0) * g.ginv), fy = floor((n - g.gy0) * g.ginv);
+  if (!(fx >= 0.0 && fx < (double)g.gnx && fy >= 0.0 && fy < (double)g.gny)) return -1;
+  return (int)fy * g.gnx + (int)fx;
+}
+
+// the register copies (R) or the memory-resident originals: one expression at the use, either source
+template <bool R, class A, class B>
+__device__ __forceinline__ const std::conditional_t<R, A, B>& regs_or(const A& regs, const B& mem) {
+  if constexpr (R) return regs;
+  else return mem;
+}
 
 // Map edges (obstacle.py PolygonObstacle). Stored as a flat read-only device table; every lane
 // walks it with the same (wave-uniform) index, so loads are scalar/broadcast.

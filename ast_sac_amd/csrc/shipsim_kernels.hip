@@ -121,11 +121,7 @@ struct ConstBuf {
   __host__ __device__ const ShipConst* ships() const { return (const ShipConst*)(base + kShipsOff); }
   static constexpr size_t kBytes = kShipsOff + sizeof(ShipConst) * SHIPSIM_MAX_SHIPS;
   // grid cell of (north, east), or -1 outside the grid / no grid / non-finite position
-  __device__ __forceinline__ int cell(double n, double e) const {
-    const double fx = floor((e - gx0) * ginv), fy = floor((n - gy0) * ginv);
-    if (!(fx >= 0.0 && fx < (double)gnx && fy >= 0.0 && fy < (double)gny)) return -1;
-    return (int)fy * gnx + (int)fx;
-  }
+  __device__ __forceinline__ int cell(double n, double e) const { return grid_cell(*this, n, e); }
 };
 #define GRID_OUT 0
 #define GRID_IN 1
@@ -199,8 +195,9 @@ __device__ __forceinline__ const ShipConst* stage_consts(const ConstBuf& K, Ship
 // (env.py test_step :389-433 / obs_step :481-512 / init_step :309-339); returns (ctrl, rudder)
 // PRE: (pre_q, pre_e) = los_q at (s.n, s.e) on the current segment, evaluated earlier in the tick; used unless the
 // waypoint index advances here
-template <bool DETAILED, bool REC, bool PRE = false>
-__device__ __forceinline__ void control_and_store(const ShipConst& c, const Params& P, Ship& s,
+// PP: Params, or its register copy in the kernels that hold one (TickConstRegs)
+template <bool DETAILED, bool REC, bool PRE = false, class PP>
+__device__ __forceinline__ void control_and_store(const ShipConst& c, const PP& P, Ship& s,
                                                   const double* __restrict__ rn, const double* __restrict__ re,
                                                   double offset, double speed_factor, double mach_dt,
                                                   int simple_collav_flag /*0 none, 1 rl(-15deg), 2 noniw(+15)*/,
@@ -278,8 +275,8 @@ __device__ __forceinline__ void control_and_integrate(const ShipConst& c, const 
 // and sin/cos(yaw) carried in (sy, cy) — valid for s.yaw on entry, refreshed after the integration
 // step, so one sincos per ship-tick serves both the kinematics and the reward's encounter angle.
 // W: the weather's source, Params or the env's LaneWeather (differentials_sc).
-template <bool DETAILED, bool REC = false, bool PRE = false, class W = Params>
-__device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, const Params& P, const W& wx, Ship& s,
+template <bool DETAILED, bool REC = false, bool PRE = false, class W = Params, class PP>
+__device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, const PP& P, const W& wx, Ship& s,
                                                          const double* __restrict__ rn,
                                                          const double* __restrict__ re, double offset,
                                                          double speed_factor, double mach_dt, int simple_collav_flag,
@@ -957,8 +954,10 @@ __global__ void init_kernel(const Params P, DevState S, ConstBuf K) {
 // reads Params where the value is used, as before (weather_of picks the source at compile time, so the uniform
 // kernels see the expressions they always had and compile to the code they had).
 struct NoWeather {};
-__device__ __forceinline__ const Params& weather_of(const Params& P, const NoWeather&) { return P; }
-__device__ __forceinline__ const LaneWeather& weather_of(const Params&, const LaneWeather& w) { return w; }
+template <class PP>  // (PP: Params or its register copy)
+__device__ __forceinline__ const PP& weather_of(const PP& P, const NoWeather&) { return P; }
+template <class PP>
+__device__ __forceinline__ const LaneWeather& weather_of(const PP&, const LaneWeather& w) { return w; }
 __device__ __forceinline__ void load_weather(NoWeather&, const double*, int, int) {}
 __device__ __forceinline__ void load_weather(LaneWeather& w, const double* __restrict__ wx, int n_envs, int env) {
   w.wind_speed = wx[(size_t)WX_WIND_SPEED * n_envs + env];
@@ -1524,6 +1523,12 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // across the tick loop (the env-leader mask, the want / stalled / started flags as lane masks, the scalar half
   // of the route addresses, the ship count for the epilogue) is laundered or re-derived where it is used
   constexpr bool OPM = POLICY && SLOTS > 2;
+  // The numbers of Params and of ConstBuf's map grid that a tick reads, held in accumulator registers (TickConstRegs,
+  // shipsim_device.hpp) for the launch instead of re-read from the kernarg segment on every tick: the two-slot
+  // LPE-16 decision streams with detailed machinery, whose ticks otherwise park on those scalar loads with nothing
+  // else to issue. ShipConst and RewardTerm stay in LDS: register copies of them measured
+  // slower (profiles/reg_consts_ab.json). Every other instantiation reads P / K as before.
+  constexpr bool RC_PAR = DETAILED && LPE == 16 && !REC && SLOTS == 2 && (MODE == 1 || MODE == 2) && !SIMPLE;
   using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
   // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
   // instantiation compiles to the code it had (the dead arm of a constant condition is not emitted)
@@ -1585,6 +1590,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   const int envc = valid ? env : 0;
   const int qc = envc * nsh + shipc;
   const ShipConst& c = SC[shipc];
+  TickConstRegs rc_par;  // (written and read only where RC_PAR: otherwise no code)
+  if constexpr (RC_PAR) rc_par.load(P, K);
   double* rn = S.route_n() + (size_t)qc * kMaxRoute;
   double* re = S.route_e() + (size_t)qc * kMaxRoute;
   if constexpr (OPM) {  // whole addresses in VGPRs: no scalar base held for reset_env / decision_prologue
@@ -1667,10 +1674,11 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     phase = 0;
     have_iw = opaque_if<OPQ>(0);
     dec_ticks = 0;
-    if (sampling_count < P.max_sampling) {
+    const auto& PT = regs_or<RC_PAR>(rc_par, P);
+    if (sampling_count < PT.max_sampling) {
       sampling_count += 1;
       float tn = (float)tan((double)sa);  // np.tan on the float32 scoping angle
-      double l_s = fabs(P.AB_seg * (double)tn);
+      double l_s = fabs(PT.AB_seg * (double)tn);
       double e_s = l_s * P.iw_cos;
       double n_s = l_s * P.iw_sin;
       if (sa > 0) e_s *= -1;
@@ -1693,7 +1701,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       travel_time = 0;
       have_iw = opaque_if<OPQ>(1);
       bool fail = corner_inside(K, lds_edges_raw, lds_boxes, P.n_polys, iw_n, iw_e) ||
-                  ((iw_n < P.min_north || iw_n > P.max_north) || (iw_e < P.min_east || iw_e > P.max_east));
+                  ((iw_n < PT.min_north || iw_n > PT.max_north) || (iw_e < PT.min_east || iw_e > PT.max_east));
       if (fail) {  // env.py:673-693 with obs_ship_IW_sampling_failure_reward (multiplier 2)
         out_r = (acc >= 0) ? -acc * 2.0 : acc * 2.0;
         snap_bits = (snap_bits | SHIPSIM_EV_SAMPLING_FAILURE | SHIPSIM_EV_TERMINAL) &
@@ -1744,7 +1752,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     load_segment(s, rn, re);
     mach_dt = P.mach_dt_reset;
     sincos(s.yaw, &sy, &cy);
-    control_and_integrate_sc<DETAILED, false>(c, P, weather_of(P, lw), s, rn, re, 0.0, 1.0, mach_dt, 0, false, nullptr,
+    const auto& PT = regs_or<RC_PAR>(rc_par, P);
+    control_and_integrate_sc<DETAILED, false>(c, PT, weather_of(PT, lw), s, rn, re, 0.0, 1.0, mach_dt, 0, false, nullptr,
                                               nullptr, sy, cy);  // init_step
     sampling_count = 0;
     travel_dist = 0; travel_time = 0; acc = 0;
@@ -1859,6 +1868,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     const Params& P = A.P;
     const ConstBuf& K = A.K;
     const Traj& T = A.T;
+    const auto& PT = regs_or<RC_PAR>(rc_par, P);  // Params' numbers: the register copies where held
+    const auto& KT = regs_or<RC_PAR>(rc_par, K);  // the map grid's
     // the lane's roles re-derived per tick where OPQ (shadowing the entry's): the run-time ship count and the
     // slot tests of the K > 1 kernels otherwise stay lane masks and scalars held across the loop, and spill
     const int lie_t = opaque_if<OPQ>(lie);
@@ -1947,7 +1958,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         los_arg = los_windup(c, s, los_pre_q);
         double d0 = pe - s.e, d1 = pn - s.n;
         need = sqrt_lt(d0 * d0 + d1 * d1, 2000.0);  // D_INIT_
-        need = diag::sb_request(need, P.max_sampling);  // (the product: need itself)
+        need = diag::sb_request(need, PT.max_sampling);  // (the product: need itself)
       }
       double pb = 1.0, cb = 0.0;
       int need0 = 0;
@@ -1966,7 +1977,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
           in.ob_so = -psy; in.ob_co = pcy;  // sin(-yaw) = -sin(yaw), cos(-yaw) = cos(yaw)
           in.p_last = p_last; in.chi_last = chi_last;
         }
-        sbmpc_cooperative<true>(need && sub == 0, in, P.sbmpc_nsamp, P.sbmpc_dt, pb, cb);
+        sbmpc_cooperative<true>(need && sub == 0, in, PT.sbmpc_nsamp, PT.sbmpc_dt, pb, cb);
         pb = env_lane_d<LPE, 0>(pb, env_lane0);
         cb = env_lane_d<LPE, 0>(cb, env_lane0);
         need0 = env_lane_i<LPE, 0>((int)need, env_lane0);
@@ -1985,9 +1996,9 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     if (going) {
       if (!is_test && s.stop) {
         // frozen obstacle ship: store_last_simulation_data + two next_time (Q9)
-        if (REC && sub == 0) record_last(T, qc, rec_t, s.time, s.time + P.dt);
-        s.time = s.time + P.dt;
-        s.time = s.time + P.dt;
+        if (REC && sub == 0) record_last(T, qc, rec_t, s.time, s.time + PT.dt);
+        s.time = s.time + PT.dt;
+        s.time = s.time + PT.dt;
       } else {
         const double prev_log_n = s.log_n, prev_log_e = s.log_e;
         const double U = s.u;
@@ -1997,15 +2008,24 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
           imminent = (dn * dn + de * de) < 9000000.0f;
         }
         SHIPSIM_SHIP_CHECK(LPE, SLOTS, 6);  // (its DPP exchanges pair sub-lanes of one ship)
-        control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, P, weather_of(P, lw), s, rn, re, -off, sf, mach_dt,
-                                                         (SIMPLE && is_test) ? 1 : 0, imminent,
-                                                         (REC && sub == 0) ? T.ship_row(qc, rec_t) : nullptr, fuel, sy,
-                                                         cy, los_pre_q, los_pre_e);
+        if constexpr (RC_PAR) {
+          // each register copy read once for the ship tick (a read is two moves per double): the step and the
+          // weather as plain values under Params' names
+          const TickStep pd = {PT.dt};
+          const LaneWeather wxr = {PT.vc_n, PT.vc_e, PT.wind_speed, PT.wind_sin, PT.wind_cos};
+          control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, pd, wxr, s, rn, re, -off, sf, mach_dt, 0, imminent, nullptr,
+                                                           fuel, sy, cy, los_pre_q, los_pre_e);
+        } else {
+          control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, P, weather_of(P, lw), s, rn, re, -off, sf, mach_dt,
+                                                           (SIMPLE && is_test) ? 1 : 0, imminent,
+                                                           (REC && sub == 0) ? T.ship_row(qc, rec_t) : nullptr, fuel, sy,
+                                                           cy, los_pre_q, los_pre_e);
+        }
         my_speed_out = U;
         if (is_obs1) {  // travel tracker (env.py:527-534, Q6)
           double tn = s.log_n - prev_log_n, te = s.log_e - prev_log_e;
           dtravel = sqrt(tn * tn + te * te);
-          dtime = P.dt;
+          dtime = PT.dt;
         }
       }
     }
@@ -2014,7 +2034,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     double d2 = INFINITY;
     bool gr = false;
     if (going) {
-      const int cc = K.cell(s.n, s.e);
+      const int cc = grid_cell(KT, s.n, s.e);
       if (cc != g_cell) {  // (rare) a new cell: its edge share and class
         g_cell = cc;
         g_mask = cc >= 0 ? grid_share(K, cc, sub, NSUB) : 0;
@@ -2044,7 +2064,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         const int k = sv & 3, half = sv >> 2;
         const double cn = (k < 2) ? s.n - margin : s.n + margin;
         const double ce = (k & 1) ? s.e + margin : s.e - margin;
-        const int c = K.cell(cn, ce);
+        const int c = grid_cell(KT, cn, ce);
         const int f = c >= 0 ? (int)K.grid_flag[c] : GRID_MIXED;
         uint32_t par = 0, bnd = 0;
         if (f == GRID_MIXED) map_inside_half(lds_edges_raw, lds_boxes, P.n_polys, cn, ce, half, par, bnd);
@@ -2068,10 +2088,10 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     if (going) {
       my_end = sqrt_le((s.n - s.end_n) * (s.n - s.end_n) + (s.e - s.end_e) * (s.e - s.end_e), 200.0);
       double margin = c.l_ship / 2;
-      my_outside = (s.n < P.min_north + margin || s.n > P.max_north - margin) ||
-                   (s.e < P.min_east + margin || s.e > P.max_east - margin);
+      my_outside = (s.n < PT.min_north + margin || s.n > PT.max_north - margin) ||
+                   (s.e < PT.min_east + margin || s.e > PT.max_east - margin);
       double rdn = s.n - s.wp_n, rde = s.e - s.wp_e;  // is_reach_radius_of_acceptance (obstacle ship)
-      my_roa = (rdn * rdn + rde * rde) < P.roa2;
+      my_roa = (rdn * rdn + rde * rde) < PT.roa2;
       // a NaN / Inf anywhere in the dynamic state poisons this sum (boundary error contract)
       my_nf = !isfinite(((s.n + s.e) + (s.yaw + s.u)) + ((s.v + s.r) + (s.omega + s.e_ct_int)));
     }
@@ -2131,7 +2151,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       const bool is_collision = ((Tn - Cn) * (Tn - Cn) + (Te - Ce) * (Te - Ce)) < 2500.0;
       const bool is_tg = Tf & XF_GROUND, is_og = Of & XF_GROUND;
       const bool is_tnav = fabs(Tect) > 3000;
-      const bool is_onav = (travel_dist > P.AB_seg * 2) || (travel_time > INFINITY) || (fabs(Oect) > 500);
+      const bool is_onav = (travel_dist > PT.AB_seg * 2) || (travel_time > INFINITY) || (fabs(Oect) > 500);
       double dx = Cn - Tn, dy = Ce - Te;
       double dist = sqrt(dx * dx + dy * dy);
       const bool enc_ok = !overtaking_sector(dx, dy, dist, Tsh, Tch, Th);  // head-on or crossing (Q5)
@@ -2178,7 +2198,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         r = o;
       }
       const bool t6 = Tf & XF_END, t7 = Tf & XF_OUTSIDE, t8 = Of & XF_END, t9 = Of & XF_OUTSIDE;
-      const bool t10 = Ttime > P.sim_time;
+      const bool t10 = Ttime > PT.sim_time;
       constexpr uint32_t kRoaBit = 1u << 31;  // (private: the obstacle ship reached its waypoint radius)
       uint32_t bits = (is_collision ? SHIPSIM_EV_COLLISION : 0) | (is_tg ? SHIPSIM_EV_TEST_GROUNDING : 0) |
                       (is_tnav ? SHIPSIM_EV_TEST_NAV_FAILURE : 0) | (is_og ? SHIPSIM_EV_OBS_GROUNDING : 0) |
@@ -2234,7 +2254,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
           else finish = true;
         }
       } else if (phase == 1) {
-        if (sampling_count == P.max_sampling) {
+        if (sampling_count == PT.max_sampling) {
           travel_dist = 0;
           travel_time = 0;
           if (combined_done) finish = true;
