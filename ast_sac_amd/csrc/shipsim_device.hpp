@@ -433,6 +433,28 @@ __device__ __forceinline__ void integrate(Ship& s, const Deriv& d, double dt, do
   s.time = s.time + dt;
 }
 
+// The position after the tick's Euler step, formed before the control chain (the decision streams that issue the
+// map query's loads early): differentials_body's two kinematic rates and integrate's two position lines, the same
+// expressions on the same operands (the control chain writes none of n, e, u, v, r, sy, cy), so the same bits.
+__device__ __forceinline__ void early_pose(const Ship& s, double sy, double cy, double dt, double& n1, double& e1) {
+  const double dn = cy * s.u + (-sy) * s.v + 0 * s.r;
+  const double de = sy * s.u + cy * s.v + 0 * s.r;
+  n1 = s.n + dn * dt;
+  e1 = s.e + de * dt;
+}
+// integrate with the position taken from early_pose (d.dn, d.de are not read: their evaluation is dead code)
+__device__ __forceinline__ void integrate(Ship& s, const Deriv& d, double n1, double e1, double dt, double mach_dt,
+                                          bool detailed) {
+  s.n = n1;
+  s.e = e1;
+  s.yaw = s.yaw + d.dyaw * dt;
+  s.u = s.u + d.du * dt;
+  s.v = s.v + d.dv * dt;
+  s.r = s.r + d.dr * dt;
+  if (detailed) s.omega = s.omega + d.domega * mach_dt;
+  s.time = s.time + dt;
+}
+
 // ---------------------------------------------------------------------------------------------
 // guidance & control
 // ---------------------------------------------------------------------------------------------

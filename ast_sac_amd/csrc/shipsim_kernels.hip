@@ -289,6 +289,20 @@ __device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, con
   integrate(s, d, P.dt, mach_dt, DETAILED);
   sincos(s.yaw, &sy, &cy);
 }
+// the same with the tick's new position (n1, e1) formed by the caller before the control chain (early_pose)
+template <bool DETAILED, bool REC = false, bool PRE = false, class W = Params, class PP>
+__device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, const PP& P, const W& wx, Ship& s,
+                                                         const double* __restrict__ rn,
+                                                         const double* __restrict__ re, double offset,
+                                                         double speed_factor, double mach_dt, double n1, double e1,
+                                                         double& sy, double& cy, double pre_q, double pre_e) {
+  double ctrl, rudder;
+  control_and_store<DETAILED, REC, PRE>(c, P, s, rn, re, offset, speed_factor, mach_dt, 0, false, nullptr, nullptr, ctrl,
+                                        rudder, pre_q, pre_e);
+  Deriv d = differentials_sc(c, wx, s, ctrl, rudder, DETAILED, sy, cy);
+  integrate(s, d, n1, e1, P.dt, mach_dt, DETAILED);
+  sincos(s.yaw, &sy, &cy);
+}
 
 // store_last_simulation_data (ship_model.py:946-957) of a stopped ship: the previous row repeated
 // with the current time; ShipAssets.time_list gets the time after the first next_time (env.py:451-465)
@@ -1122,6 +1136,46 @@ __device__ __forceinline__ double map_dist2_mask(const EdgeX* __restrict__ E, ui
   return best;
 }
 
+// a double as a value of its own: an expression the compiler can neither sink into a branch nor re-evaluate
+__device__ __forceinline__ double pinned_d(double x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
+// map_dist2_mask with the next set bit's edge read from LDS before the current edge's arithmetic, and every field
+// of an edge read at once: the same expressions on the same values, the min taken in the same order
+__device__ __forceinline__ double map_dist2_mask_pf(const EdgeX* __restrict__ E, uint64_t m, double n, double e) {
+  const double px = e, py = n;
+  double best = INFINITY;
+  if (m) {
+    EdgeX ed = E[__builtin_ctzll(m)];
+    m &= m - 1;
+    bool more;
+    do {
+      more = m != 0;
+      const EdgeX nx = E[more ? __builtin_ctzll(m) : 0];  // (no further bit: edge 0, read and not used)
+      m &= m - 1;
+      __builtin_amdgcn_sched_barrier(0);  // (the reads issue here, not after the arithmetic they run under)
+      const double qx = px - ed.ax, qy = py - ed.ay;
+      const double t = qx * ed.dx + qy * ed.dy;
+      const double da = qx * qx + qy * qy;
+      const double rx = px - ed.bx, ry = py - ed.by;
+      const double db = rx * rx + ry * ry;
+      const double cc = (ed.ay - py) * ed.dx - (ed.ax - px) * ed.dy;
+      const double dp = cc * cc * ed.inv_len2;
+      // (the three candidates as values the selects cannot be turned back into branches around)
+      const double va = pinned_d(da), vb = pinned_d(db), vp = pinned_d(dp);
+      const double d2 = (t <= 0.0) ? va : ((t >= ed.len2) ? vb : vp);
+      best = py_min(best, d2);
+      ed = nx;
+    } while (more);
+    // the last look-ahead read has a use, so the reads stay ahead of the arithmetic instead of moving into the
+    // next iteration (it completed under the last edge's arithmetic)
+    asm volatile("" ::"v"(ed.ax), "v"(ed.ay), "v"(ed.bx), "v"(ed.by), "v"(ed.dx), "v"(ed.dy), "v"(ed.len2), "v"(ed.inv_len2));
+  }
+  return best;
+}
+
 // if_pos_inside_obstacles with the grid's exact cell classification (full test on mixed cells)
 __device__ __forceinline__ bool corner_inside(const ConstBuf& K, const Edge* __restrict__ edges,
                                               const PolyBox* __restrict__ boxes, int n_polys, double n, double e) {
@@ -1529,6 +1583,12 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // else to issue. ShipConst and RewardTerm stay in LDS: register copies of them measured
   // slower (profiles/reg_consts_ab.json). Every other instantiation reads P / K as before.
   constexpr bool RC_PAR = DETAILED && LPE == 16 && !REC && SLOTS == 2 && (MODE == 1 || MODE == 2) && !SIMPLE;
+  // The same streams form the position after the tick's Euler step before the control chain and request a new grid
+  // cell's edge share and class there (the ship tick below), and walk the cell's edges with the next edge's LDS
+  // reads issued ahead of the current edge's arithmetic (map_dist2_mask_pf): the map query's loads run under other
+  // work instead of in front of their first use. The sliced step kernels (MODE 0) keep the query as
+  // it was: the tests' independent reference.
+  constexpr bool EARLY_MAP = RC_PAR;
   using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
   // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
   // instantiation compiles to the code it had (the dead arm of a constant condition is not emitted)
@@ -1993,7 +2053,27 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     PT_MARK(0);
     // ---- ship ticks (test_step :345-445 / obs_step :447-536) ----
     double my_speed_out = 0.0, dtravel = 0.0, dtime = 0.0;
+    double ep_n = 0.0, ep_e = 0.0, ep_dt = 0.0;  // (EARLY_MAP) the position after this tick's step, and the step
     if (going) {
+      if constexpr (EARLY_MAP) {
+        // The map query's cell and, where it changes, the cell's edge share and class, requested here: the query
+        // needs only the position after the tick's Euler step, which the state at the tick's start fixes (a frozen
+        // obstacle ship keeps its position), so its two global loads run under the control chain instead of in
+        // front of the edge loop. g_cell is the query's cell from here on.
+        ep_dt = PT.dt;
+        early_pose(s, sy, cy, ep_dt, ep_n, ep_e);
+        const bool frozen = !is_test && s.stop;
+        const int cc = grid_cell(KT, frozen ? s.n : ep_n, frozen ? s.e : ep_e);
+        if (cc != g_cell) {
+          g_cell = cc;
+          g_mask = 0;
+          g_flag = GRID_MIXED;
+          if (cc >= 0) {  // (one block: the two arrays' addresses in one fetch, the two loads back to back)
+            g_mask = grid_share(K, cc, sub, NSUB);
+            g_flag = (int)K.grid_flag[cc];
+          }
+        }
+      }
       if (!is_test && s.stop) {
         // frozen obstacle ship: store_last_simulation_data + two next_time (Q9)
         if (REC && sub == 0) record_last(T, qc, rec_t, s.time, s.time + PT.dt);
@@ -2011,10 +2091,11 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         if constexpr (RC_PAR) {
           // each register copy read once for the ship tick (a read is two moves per double): the step and the
           // weather as plain values under Params' names
-          const TickStep pd = {PT.dt};
           const LaneWeather wxr = {PT.vc_n, PT.vc_e, PT.wind_speed, PT.wind_sin, PT.wind_cos};
-          control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, pd, wxr, s, rn, re, -off, sf, mach_dt, 0, imminent, nullptr,
-                                                           fuel, sy, cy, los_pre_q, los_pre_e);
+          static_assert(EARLY_MAP == RC_PAR, "the step and the new position were formed at the top of the ship tick");
+          const TickStep pd = {ep_dt};
+          control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, pd, wxr, s, rn, re, -off, sf, mach_dt, ep_n, ep_e, sy, cy,
+                                                           los_pre_q, los_pre_e);
         } else {
           control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, P, weather_of(P, lw), s, rn, re, -off, sf, mach_dt,
                                                            (SIMPLE && is_test) ? 1 : 0, imminent,
@@ -2034,14 +2115,23 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     double d2 = INFINITY;
     bool gr = false;
     if (going) {
-      const int cc = grid_cell(KT, s.n, s.e);
-      if (cc != g_cell) {  // (rare) a new cell: its edge share and class
-        g_cell = cc;
-        g_mask = cc >= 0 ? grid_share(K, cc, sub, NSUB) : 0;
-        g_flag = cc >= 0 ? (int)K.grid_flag[cc] : GRID_MIXED;
+      int cc;
+      if constexpr (EARLY_MAP) {
+        cc = g_cell;  // this position's cell, its share and class already requested (the top of the ship tick)
+      } else {
+        cc = grid_cell(KT, s.n, s.e);
+        if (cc != g_cell) {  // (rare) a new cell: its edge share and class
+          g_cell = cc;
+          g_mask = cc >= 0 ? grid_share(K, cc, sub, NSUB) : 0;
+          g_flag = cc >= 0 ? (int)K.grid_flag[cc] : GRID_MIXED;
+        }
       }
-      if constexpr (!diag::kNoMapDist)
-        d2 = cc >= 0 ? map_dist2_mask(lds_edges, g_mask, s.n, s.e) : map_dist2_part(lds_edges, K.n_edges, s.n, s.e, sub, NSUB);
+      if constexpr (!diag::kNoMapDist) {
+        if constexpr (EARLY_MAP)
+          d2 = cc >= 0 ? map_dist2_mask_pf(lds_edges, g_mask, s.n, s.e) : map_dist2_part(lds_edges, K.n_edges, s.n, s.e, sub, NSUB);
+        else
+          d2 = cc >= 0 ? map_dist2_mask(lds_edges, g_mask, s.n, s.e) : map_dist2_part(lds_edges, K.n_edges, s.n, s.e, sub, NSUB);
+      }
       const double margin = c.l_ship / 2;  // check_condition.py:50-78 hull hard points
       // Every hull corner is within margin·√2 of the centre. With no coastline edge that close (the
       // ship's min over its cell's candidate edges, which hold every edge within kGroundReach) and the
