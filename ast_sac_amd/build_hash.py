@@ -10,7 +10,8 @@ _ROOT = os.path.dirname(_HERE)
 SOURCES = {
     "shipsim": ["ast_sac_amd/csrc/shipsim_kernels.hip", "ast_sac_amd/csrc/shipsim_device.hpp",
                 "ast_sac_amd/csrc/shipsim_diag.hpp", "ast_sac_amd/csrc/shipsim_weather_host.hpp",
-                "ast_sac_amd/csrc/shipsim_launch_host.hpp", "include/shipsim.h"],
+                "ast_sac_amd/csrc/shipsim_launch_host.hpp", "ast_sac_amd/csrc/shipsim_state_host.hpp",
+                "include/shipsim.h"],
     "sacfused": ["ast_sac_amd/csrc/sac_kernels.hip", "include/sac_fused.h"],
 }
 

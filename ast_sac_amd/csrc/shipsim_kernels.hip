@@ -9,6 +9,7 @@
 //                    (_step :563-622) until its decision point (RoA + 1 tick) or done
 //   single_tick_kernel: C2 single-ship loop body (run_colav/run_simplified_model.py:248-249 shape)
 //   single_tick_pipe_kernel: the same for the simplified machinery, three waves per 64 ships
+//   fork_gather_kernel: shipsim_fork — env i takes env src_env[i]'s share of every column of the state block
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -24,6 +25,7 @@
 #include "shipsim_device.hpp"
 #include "shipsim_launch_host.hpp"   // the list of step kernels and the choice among them
 #include "shipsim_weather_host.hpp"  // shipsim_set_weather's host half
+#include "shipsim_state_host.hpp"    // the state block as a table of columns (snapshot / restore / fork)
 
 #include "shipsim_diag.hpp"  // diagnostics / ablation hooks (none in the product build)
 
@@ -90,6 +92,10 @@ struct DevState {
   static constexpr int kEnvArrays = 19;
   static constexpr int kShipArrays = 22;
 };
+// shipsim_fork moves the columns of state_host::table(): an array added here gets its row there
+static_assert(DevState::kEnvArrays == state_host::kEnvArrays && DevState::kShipArrays == state_host::kShipArrays &&
+                  kMaxRoute * sizeof(double) == state_host::kRouteSlotBytes,
+              "DevState and the column table (shipsim_state_host.hpp) list the same arrays");
 // dec_flags bits (per env, persistent across calls)
 #define DF_AWAITING 1
 #define DF_HAVE_IW 2
@@ -2993,6 +2999,37 @@ __global__ __launch_bounds__(256) void div_check_kernel(int n, const double* __r
   ref[i] = a / d;
 }
 
+// shipsim_fork: env i of dst becomes env src_env[i] of src, for every column of the state block in one launch.
+// blockIdx.y is the column (state_host::table); a column of n_envs * env_bytes bytes is n_envs * (env_bytes / unit)
+// units, unit t of it lying at offset + t * unit, so consecutive lanes store consecutive units (consecutive envs for
+// the one-element columns, the 16-byte pieces of one env's route rows for the routes) and only the loads are
+// gathered. The blocks of a column stride over its units. src and dst never overlap (a fork from the live state
+// goes through the staging block). An index outside [0, n_envs) is tested before any address is formed from it:
+// env i then keeps src's env i (own_fallback: dst is the staging copy of src) or is not written at all (dst is the
+// live block, src a snapshot).
+__global__ __launch_bounds__(256) void fork_gather_kernel(const state_host::Table T, const char* __restrict__ src,
+                                                          char* __restrict__ dst, const int32_t* __restrict__ src_env,
+                                                          uint32_t n_envs, int own_fallback) {
+  const state_host::Column c = T.col[blockIdx.y];
+  const uint32_t per_env = state_host::units_per_env(c);
+  const uint32_t total = n_envs * per_env;  // (<= 2^31, and the stride <= 2^18: the host's kForkMaxUnits / -Blocks)
+  const uint32_t stride = gridDim.x * 256u;
+  for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < total; t += stride) {
+    const uint32_t env = t / per_env, piece = t - env * per_env;
+    uint32_t from = env;
+    if (src_env) {
+      const uint32_t s = (uint32_t)src_env[env];
+      if (s < n_envs) from = s;       // (a negative index is >= 2^31 here)
+      else if (!own_fallback) continue;
+    }
+    const char* p = src + state_host::unit_src(c, from, piece);
+    char* q = dst + state_host::unit_dst(c, t);
+    if (c.unit == 16) *(uint4*)q = *(const uint4*)p;
+    else if (c.unit == 8) *(uint2*)q = *(const uint2*)p;
+    else *(uint32_t*)q = *(const uint32_t*)p;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -3021,6 +3058,9 @@ struct shipsim_handle {
   double* wx_host;
   int wx_on;
   int lpe_uniform;
+  // shipsim_fork from the live state gathers into this block of dev_bytes and copies it back (allocated at the
+  // first such call)
+  void* fork_block;
   char err[512];
 };
 
@@ -3675,13 +3715,13 @@ int shipsim_create(const shipsim_config* cfg_in, int32_t n_envs, int32_t n_obs_s
   h->K.grid_part = use_grid ? (const uint64_t*)((const char*)h->const_block + part_off) : nullptr;
 
   // state block (DevState layout: ship arrays | routes | env arrays)
-  const size_t S = (size_t)n_envs * ns, N = (size_t)n_envs;
-  auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  h->S.ship_stride = (int64_t)r256(S * sizeof(double));
-  h->S.route_stride = (int64_t)r256(S * kMaxRoute * sizeof(double));
-  h->S.env_stride = (int64_t)r256(N * 8 * sizeof(float));
-  h->S.env_off = DevState::kShipArrays * h->S.ship_stride + 2 * h->S.route_stride;
-  size_t bytes = (size_t)(h->S.env_off + DevState::kEnvArrays * h->S.env_stride);
+  const size_t S = (size_t)n_envs * ns;
+  const state_host::Layout lay = state_host::layout(n_envs, ns);
+  h->S.ship_stride = lay.ship_stride;
+  h->S.route_stride = lay.route_stride;
+  h->S.env_stride = lay.env_stride;
+  h->S.env_off = lay.env_off;
+  size_t bytes = (size_t)lay.bytes;
   e = hipMalloc(&h->dev_block, bytes);
   if (e != hipSuccess) {
     *out = h;
@@ -3721,6 +3761,7 @@ int shipsim_destroy(shipsim_handle* h) {
     if (h->nonfinite_dev) (void)hipFree(h->nonfinite_dev);
     if (h->tail_ctr) (void)hipFree(h->tail_ctr);
     if (h->wx_dev) (void)hipFree(h->wx_dev);
+    if (h->fork_block) (void)hipFree(h->fork_block);
   }
   free(h->wx_host);
   delete h;
@@ -3914,6 +3955,90 @@ int shipsim_set_state(shipsim_handle* h, int32_t field, const void* src) {
   if (field_ptr(h, field, &p, &b)) return fail(h, SHIPSIM_EINVAL, "unknown field %d", field);
   DeviceGuard g(h->device);
   HIPCHK(h, hipMemcpyAsync(p, src, b, hipMemcpyDefault, h->stream));
+  return SHIPSIM_OK;
+}
+
+// ---- snapshot / restore / fork: the whole state block (shipsim_state_host.hpp) ----
+int64_t shipsim_state_bytes(const shipsim_handle* h) { return h && h->dev_block ? (int64_t)h->dev_bytes : SHIPSIM_EINVAL; }
+
+// what the three calls refuse alike: NULL buffer (where one is required), another size, a recording handle
+static int state_call_check(shipsim_handle* h, const char* what, const void* buf, bool need_buf, int64_t bytes) {
+  if (need_buf && !buf) return fail(h, SHIPSIM_EINVAL, "%s: the buffer is NULL", what);
+  if (bytes != (int64_t)h->dev_bytes)
+    return fail(h, SHIPSIM_EINVAL, "%s: %lld bytes, the state of this handle has %lld (shipsim_state_bytes)", what,
+                (long long)bytes, (long long)h->dev_bytes);
+  if (h->T.ship)
+    return fail(h, SHIPSIM_EINVAL, "%s: trajectory recording is on (rows, lengths and fuel are not part of a snapshot)",
+                what);
+  return SHIPSIM_OK;
+}
+
+int shipsim_snapshot(shipsim_handle* h, void* dst, int64_t bytes) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (int rc = state_call_check(h, "snapshot", dst, true, bytes)) return rc;
+  if (!h->ever_reset) return fail(h, SHIPSIM_ESTATE, "snapshot before reset");
+  DeviceGuard g(h->device);
+  HIPCHK(h, hipMemcpyAsync(dst, h->dev_block, h->dev_bytes, hipMemcpyDeviceToDevice, h->stream));
+  return SHIPSIM_OK;
+}
+
+int shipsim_restore(shipsim_handle* h, const void* src, int64_t bytes) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (int rc = state_call_check(h, "restore", src, true, bytes)) return rc;
+  DeviceGuard g(h->device);
+  HIPCHK(h, hipMemcpyAsync(h->dev_block, src, h->dev_bytes, hipMemcpyDeviceToDevice, h->stream));
+  h->ever_reset = 1;
+  return SHIPSIM_OK;
+}
+
+constexpr int64_t kForkMaxUnits = (int64_t)1 << 31;  // fork_gather_kernel counts a column's units in 32 bits
+constexpr int64_t kForkMaxBlocks = 1024;             // blocks per column (they stride over its units)
+
+int shipsim_fork(shipsim_handle* h, const void* from, int64_t bytes, const int32_t* src_env) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (int rc = state_call_check(h, "fork", from, false, bytes)) return rc;
+  if (from && ((uintptr_t)from & 15)) return fail(h, SHIPSIM_EINVAL, "fork: the snapshot is not 16-byte aligned");
+  if (!from && !h->ever_reset) return fail(h, SHIPSIM_ESTATE, "fork from the live state before reset");
+  if (!src_env) {  // identity: a restore, or nothing
+    if (!from) return SHIPSIM_OK;
+    return shipsim_restore(h, from, bytes);
+  }
+  const state_host::Layout lay = {h->S.ship_stride, h->S.route_stride, h->S.env_stride, h->S.env_off,
+                                  (int64_t)h->dev_bytes};
+  const state_host::Table tab = state_host::table(lay, h->P.n_ships);
+  const int64_t units = state_host::max_units(tab, h->P.n_envs);
+  if (units > kForkMaxUnits) return fail(h, SHIPSIM_EINVAL, "fork: %d envs are more than the gather counts", h->P.n_envs);
+  DeviceGuard g(h->device);
+  if (!from && !h->fork_block) {
+    // zeroed once, so that the padding between the arrays, which the gather leaves alone, goes back as it is in
+    // the state block (zero since shipsim_create). The memset is ordered on the stream of this first fork only, as
+    // are this fork's gather and copy back behind it: after a shipsim_set_stream the staging block is ordered
+    // against the new stream the way the state block itself is, by the caller's ordering of the two streams.
+    // (Sizing: every grid row below gets the block count of the widest column, the routes; the blocks a narrower
+    // column does not need find t >= total and exit. Per-column counts and a reciprocal for the per-unit divide are
+    // what to do next should the gather's cost over a plain copy of the block ever matter: DESIGN.md §9.)
+    hipError_t e = hipMalloc(&h->fork_block, h->dev_bytes);
+    if (e != hipSuccess) {
+      h->fork_block = nullptr;
+      return fail(h, e == hipErrorOutOfMemory ? SHIPSIM_ENOMEM : SHIPSIM_EHIP, "hipMalloc(fork staging %zu B): %s",
+                  h->dev_bytes, hipGetErrorString(e));
+    }
+    e = hipMemsetAsync(h->fork_block, 0, h->dev_bytes, h->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(h->fork_block);
+      h->fork_block = nullptr;
+      return fail(h, SHIPSIM_EHIP, "hipMemsetAsync(fork staging): %s", hipGetErrorString(e));
+    }
+  }
+  int64_t blocks = (units + 255) / 256;
+  if (blocks > kForkMaxBlocks) blocks = kForkMaxBlocks;
+  const char* src = from ? (const char*)from : (const char*)h->dev_block;
+  char* dst = from ? (char*)h->dev_block : (char*)h->fork_block;
+  hipLaunchKernelGGL(fork_gather_kernel, dim3((unsigned)blocks, state_host::kColumns), dim3(256), 0, h->stream, tab,
+                     src, dst, src_env, (uint32_t)h->P.n_envs, from ? 0 : 1);
+  HIPCHK(h, hipGetLastError());
+  if (!from) HIPCHK(h, hipMemcpyAsync(h->dev_block, h->fork_block, h->dev_bytes, hipMemcpyDeviceToDevice, h->stream));
+  h->ever_reset = 1;
   return SHIPSIM_OK;
 }
 

@@ -95,6 +95,53 @@ class BatchedMultiShipRLEnv:
         """The per-env weather in force (dict of four float64 arrays), or None under the config's."""
         return self.sim.weather()
 
+    # -- snapshot / restore / fork (beyond the reference; ShipSim.snapshot) --
+    @property
+    def state_bytes(self):
+        return self.sim.state_bytes
+
+    def snapshot(self, out=None):
+        """The complete state of every env (a shipsim.Snapshot on the device): what restore() and fork() continue
+        from, mid-decision state included. Weather, like the config, stays with the env object."""
+        return self.sim.snapshot(out=out)
+
+    def restore(self, snap):
+        """Rewind every env to a snapshot of this env (or of one of the same kind, n_envs and ship count)."""
+        self.sim.restore(snap)
+
+    def fork(self, src, source=None, weather="keep"):
+        """Env i continues from the state of env src[i] — of this env as it is, or of the Snapshot `source`; an index
+        outside [0, n_envs) leaves env i alone. weather="keep": a clone sails under the weather of the slot it lands
+        in; "follow": the source envs' weather moves with their clones (through set_weather, a host-side setup
+        call that needs the indices on the host and waits for the upload; without per-env weather there is nothing
+        to move). Weather is not part of a Snapshot: with a `source`, "follow" gathers the weather this env object
+        has per slot now — not what was in force when the snapshot was taken, nor that of another env object it
+        came from; a caller who archives snapshots keeps weather() beside them and calls set_weather itself.
+        Returns the device index tensor."""
+        if weather not in ("keep", "follow"):
+            raise ValueError(f"weather must be 'keep' or 'follow', not {weather!r}")
+        w = self.weather() if weather == "follow" else None
+        s = self.sim.fork(src, source=source)
+        if w is not None:
+            idx = s.cpu().numpy().astype(np.int64)
+            own = np.arange(self.n_envs)
+            idx = np.where((idx >= 0) & (idx < self.n_envs), idx, own)
+            self.set_weather({k: v[idx] for k, v in w.items()})
+        return s
+
+    def fork_stream_state(self, src, ep_idx, dec_idx, log_len=None):
+        """The caller's side of a fork under run_table / run_policy: its per-env stream arrays (episode counter,
+        decision index and, if given, record count) gathered in place the way fork(src) gathers the envs, so that
+        clone i goes on at its source's place in the episode; entries with an index outside [0, n_envs) stay."""
+        s = torch.as_tensor(src, device=self.device).reshape(-1).long()
+        if s.numel() != self.n_envs:
+            raise ValueError(f"src has {s.numel()} entries, expected {self.n_envs}")
+        own = torch.arange(self.n_envs, device=self.device)
+        idx = torch.where((s >= 0) & (s < self.n_envs), s, own)
+        for x in (ep_idx, dec_idx, log_len):
+            if x is not None:
+                x.copy_(x[idx])
+
     # -- reference helpers (env.py:186-196) --
     def do_normalize_action(self, a_real):
         return 2.0 * (a_real - self.action_space.low) / (self.action_space.high - self.action_space.low) - 1.0

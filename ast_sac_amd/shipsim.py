@@ -68,9 +68,15 @@ def load_library(path=LIB_PATH):
                                                    C.c_int32, P, P, P, P, P, C.c_int32, P]),
                            ("shipsim_sbmpc_eval_multi", [C.c_int32, C.c_int32, C.c_double, C.c_double, P, P, P]),
                            ("shipsim_set_weather", [P, P, P, P, P]),
-                           ("shipsim_get_weather", [P, P, P, P, P])):
+                           ("shipsim_get_weather", [P, P, P, P, P]),
+                           ("shipsim_state_bytes", [P]),
+                           ("shipsim_snapshot", [P, P, C.c_int64]),
+                           ("shipsim_restore", [P, P, C.c_int64]),
+                           ("shipsim_fork", [P, P, C.c_int64, P])):
         try:
             getattr(L, name).argtypes = argtypes
+            if name == "shipsim_state_bytes":
+                L.shipsim_state_bytes.restype = C.c_int64
         except AttributeError:
             if "SHIPSIM_LIB" not in os.environ:
                 raise
@@ -91,7 +97,22 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_set_trajectory", "shipsim_sbmpc_eval", "shipsim_legacy_step", "shipsim_run_table",
                     "shipsim_nonfinite_count", "shipsim_lanes_per_env", "shipsim_set_stream",
                     "shipsim_run_policy", "shipsim_diag_lane_faults", "shipsim_set_stream_tail", "shipsim_div_check",
-                    "shipsim_sbmpc_eval_multi", "shipsim_set_weather", "shipsim_get_weather")
+                    "shipsim_sbmpc_eval_multi", "shipsim_set_weather", "shipsim_get_weather",
+                    "shipsim_state_bytes", "shipsim_snapshot", "shipsim_restore", "shipsim_fork")
+
+
+class Snapshot:
+    """The complete dynamic state of every env of a handle (ShipSim.snapshot): `data`, a uint8 device tensor of
+    state_bytes, and the shape it belongs to — kind, n_envs, n_ships — with the build string of the library that
+    wrote it (the layout of the bytes is that build's)."""
+
+    __slots__ = ("data", "kind", "n_envs", "n_ships", "build")
+
+    def __init__(self, data, kind, n_envs, n_ships, build):
+        self.data, self.kind, self.n_envs, self.n_ships, self.build = data, int(kind), int(n_envs), int(n_ships), build
+
+    def clone(self):
+        return Snapshot(self.data.clone(), self.kind, self.n_envs, self.n_ships, self.build)
 
 
 def diag_lane_faults():
@@ -300,6 +321,68 @@ class ShipSim:
         self._follow_stream()
         self._check(self.L.shipsim_set_state(self.h, int(field), _ptr(t)), "shipsim_set_state")
         self._keep_set = t
+
+    # -- snapshot / restore / fork (include/shipsim.h: shipsim_snapshot) --
+    @property
+    def state_bytes(self):
+        """Bytes of the handle's whole state block (shipsim_state_bytes)."""
+        n = int(self.L.shipsim_state_bytes(self.h))
+        if n < 0:
+            raise ShipSimError(f"shipsim_state_bytes failed ({n})")
+        return n
+
+    def snapshot(self, out=None):
+        """The complete state of every env, mid-decision state included, as a Snapshot on the device (asynchronous
+        on the current stream). out: a Snapshot of this handle's shape to overwrite instead of allocating. The
+        stream arrays a caller owns (ep_idx, dec_idx, log_len, the policy's counter) are the caller's to keep."""
+        if out is None:
+            out = Snapshot(torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device), self.cfg.kind,
+                           self.n_envs, self.n_ships, self.L.shipsim_build_info().decode())
+        else:
+            self._check_snapshot(out, "snapshot")
+        self._follow_stream()
+        self._check(self.L.shipsim_snapshot(self.h, _ptr(out.data), out.data.numel()), "shipsim_snapshot")
+        return out
+
+    def _check_snapshot(self, snap, what):
+        if not isinstance(snap, Snapshot):
+            raise ShipSimError(f"{what}: expected a Snapshot, got {type(snap).__name__}")
+        mine = (int(self.cfg.kind), self.n_envs, self.n_ships)
+        if (snap.kind, snap.n_envs, snap.n_ships) != mine:
+            raise ShipSimError(f"{what}: the snapshot is of (kind, n_envs, n_ships) = "
+                               f"{(snap.kind, snap.n_envs, snap.n_ships)}, this handle of {mine}")
+        build = self.L.shipsim_build_info().decode()
+        if snap.build != build:
+            raise ShipSimError(f"{what}: the snapshot was written by another build ({snap.build!r}, this is {build!r})")
+        d = snap.data
+        if d.dtype != torch.uint8 or d.device != self.device or not d.is_contiguous() or d.numel() != self.state_bytes:
+            raise ShipSimError(f"{what}: the snapshot's data must be a contiguous uint8 tensor of {self.state_bytes} "
+                               f"bytes on {self.device}")
+
+    def restore(self, snap):
+        """Put a Snapshot back (shipsim_restore): from the next launch on the handle continues, bit for bit, as it
+        did after the snapshot was taken, given the caller's own stream arrays as they were. A Snapshot of another
+        kind, n_envs, ship count or build is refused before the library is called."""
+        self._check_snapshot(snap, "restore")
+        self._follow_stream()
+        self._check(self.L.shipsim_restore(self.h, _ptr(snap.data), snap.data.numel()), "shipsim_restore")
+
+    def fork(self, src, source=None):
+        """Env i takes the state of env src[i] (shipsim_fork): of this handle as it is (source None), or of a
+        Snapshot. src: (n_envs,) device int32 tensor or anything torch.as_tensor takes; any index array is served
+        (permutations, broadcasts, cycles), and an index outside [0, n_envs) leaves env i as it is. A clone runs
+        under its new slot's weather, noise and actions; one paused mid-decision resumes without consuming an
+        action. Returns the index tensor used."""
+        s = self._dev(src, torch.int32).reshape(-1)
+        if s.numel() != self.n_envs:
+            raise ShipSimError(f"fork: src has {s.numel()} entries, expected {self.n_envs}")
+        if source is not None:
+            self._check_snapshot(source, "fork")
+        self._follow_stream()
+        self._check(self.L.shipsim_fork(self.h, _ptr(source.data) if source is not None else None, self.state_bytes,
+                                        _ptr(s)), "shipsim_fork")
+        self._keep_fork = s
+        return s
 
     # -- per-env weather (include/shipsim.h: shipsim_set_weather) --
     WEATHER_KEYS = ("wind_speed", "wind_direction", "current_north", "current_east")

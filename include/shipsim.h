@@ -28,6 +28,8 @@ extern "C" {
 #endif
 
 #define SHIPSIM_ABI_VERSION 12  /* 12: shipsim_set_weather / shipsim_get_weather (per-env wind and current) */
+/* (shipsim_state_bytes / shipsim_snapshot / shipsim_restore / shipsim_fork came later and are additive: no struct
+ * layout and no existing call changed, so the version stays 12; a binding looks the four symbols up on their own) */
 
 #define SHIPSIM_MAX_ROUTE 16   /* waypoints per ship route (obs ship: 2 + max_sampling_frequency) */
 #define SHIPSIM_MAX_POLYS 16   /* land polygons in the map */
@@ -310,6 +312,43 @@ int shipsim_tick(shipsim_handle* h, int32_t k, uint32_t* events_out);
  * env-major [env][ship] (the device lane order), env fields [env], routes [env][ship][SHIPSIM_MAX_ROUTE]. */
 int shipsim_get_state(shipsim_handle* h, int32_t field, void* dst);
 int shipsim_set_state(shipsim_handle* h, int32_t field, const void* src);
+
+/* ---- snapshot, restore and fork: exact clones of env states on the device --------------------------------
+ * The fields above are a view; what an env continues from is the whole state block of the handle: every ship
+ * array (the 19 fields, the logged position, the route length), both route arrays and every env array — the
+ * decision flags and phase, the ticks of the decision in progress, the reset flag, the machinery dt, the
+ * observations and states the collision checks and the decision record read. These calls move that block,
+ * shipsim_state_bytes(h) bytes for this handle (a negative SHIPSIM_E* code for a NULL handle).
+ *   shipsim_snapshot  copies it into dst, a caller-owned device buffer of that size.
+ *   shipsim_restore   puts a snapshot back: from the next launch on shipsim_step, shipsim_run_table,
+ *                     shipsim_run_policy, shipsim_tick, shipsim_legacy_step and shipsim_get_state give, bit for bit,
+ *                     what they gave after the snapshot was taken — provided the caller also puts back the arrays
+ *                     it owns (ep_idx, dec_idx, log_len, the policy's counter).
+ *   shipsim_fork      after the call env i holds the state env src_env[i] had before it. src_env: n_envs int32 on
+ *                     the device; NULL = identity. from: a snapshot (16-byte aligned) of a handle of the same shape,
+ *                     or NULL for the handle's own state as it is. Any index array is served — permutations,
+ *                     broadcasts, cycles: a fork from the handle's own state is gathered into a library-owned
+ *                     staging block of the same size (allocated at the first such call; SHIPSIM_ENOMEM /
+ *                     SHIPSIM_EHIP if that fails) and copied back, one kernel launch and one copy; from a snapshot
+ *                     it is one launch (src_env == NULL: a restore). An index outside [0, n_envs) leaves env i as
+ *                     it is (defined behaviour; the kernel tests the index before it forms an address). The state
+ *                     block never moves: captured graphs that hold its address stay valid.
+ * All three are asynchronous on the handle's stream, without host synchronisation or host allocation (but for
+ * the staging block's allocation), and may be captured into a graph once the staging block exists.
+ * Not state, staying with the handle and the slot: the config, per-env weather, the stream tail, lanes per env, the
+ * non-finite counter, trajectory buffers. So a clone sails under the weather of the slot it lands in; under a
+ * stochastic policy it draws its slot's noise (Philox is keyed by env index), which is what splitting wants; an env
+ * cloned while paused mid-decision resumes without consuming an action, one cloned while awaiting a decision
+ * consumes its new slot's action. A snapshot may go into another handle of the same kind, n_envs and ship count,
+ * whatever its lanes per env (results do not depend on them); restoring, or forking from a snapshot, onto a handle
+ * never reset is allowed and marks it reset. All kinds (AST with K = 1..4, NONIW, SINGLE).
+ * SHIPSIM_EINVAL with the reason in shipsim_last_error: bytes != shipsim_state_bytes(h); a NULL dst / src; a
+ * handle with trajectory recording enabled (rows, lengths and fuel are not part of a snapshot). SHIPSIM_ESTATE:
+ * a snapshot, or a fork from the handle's own state, before the first reset. */
+int64_t shipsim_state_bytes(const shipsim_handle* h);
+int shipsim_snapshot(shipsim_handle* h, void* dst, int64_t bytes);
+int shipsim_restore(shipsim_handle* h, const void* src, int64_t bytes);
+int shipsim_fork(shipsim_handle* h, const void* from, int64_t bytes, const int32_t* src_env);
 
 /* ---- trajectory recording (f1: simulation_results export) ----------------------------------
  * Per-tick rows of ShipModelAST/SimpleShipModel.store_simulation_data (ship_model.py:903-957,
