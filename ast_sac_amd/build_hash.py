@@ -8,10 +8,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 
 SOURCES = {
-    "shipsim": ["ast_sac_amd/csrc/shipsim_kernels.hip", "ast_sac_amd/csrc/shipsim_device.hpp",
-                "ast_sac_amd/csrc/shipsim_diag.hpp", "ast_sac_amd/csrc/shipsim_weather_host.hpp",
-                "ast_sac_amd/csrc/shipsim_launch_host.hpp", "ast_sac_amd/csrc/shipsim_state_host.hpp",
-                "include/shipsim.h"],
+    "shipsim": ["ast_sac_amd/csrc/shipsim_kernels.hip", "ast_sac_amd/csrc/shipsim_c2_pipe.hip",
+                "ast_sac_amd/csrc/shipsim_types.hpp", "ast_sac_amd/csrc/shipsim_device.hpp",
+                "ast_sac_amd/csrc/shipsim_state.hpp", "ast_sac_amd/csrc/shipsim_sbmpc.hpp",
+                "ast_sac_amd/csrc/shipsim_diag.hpp", "ast_sac_amd/csrc/shipsim_config_host.hpp",
+                "ast_sac_amd/csrc/shipsim_weather_host.hpp", "ast_sac_amd/csrc/shipsim_launch_host.hpp",
+                "ast_sac_amd/csrc/shipsim_state_host.hpp", "include/shipsim.h"],
     "sacfused": ["ast_sac_amd/csrc/sac_kernels.hip", "include/sac_fused.h"],
 }
 
@@ -28,20 +30,27 @@ HIPFLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shar
 # r4z_sched_ab.txt), with the scheduler's AMDGPU register-pressure trackers (+0.5 %, r4zz_sched3_ab.txt).
 LIB_FLAGS = {"shipsim": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-mllvm", "-amdgpu-use-amdgpu-trackers"],
              "sacfused": []}
-# libraries built from several objects of the same source, each with flags of its own (then linked into one .so).
+# Both libraries are linked from two objects, each a (source file, extra flags) pair.
 # sacfused: max-ILP is 0.6 µs faster per grad step at H = 256 but spills SGPRs in three kernels at H = 448 / 512,
-# so the widths up to 384 (and the C ABI) are one object with it and the two widest another without
-# (sac_kernels.hip SACF_TU).
-# shipsim: the C2 three-wave kernel (its own object, SHIPSIM_TU 2) keeps machine LICM — its loops have registers to
-# spare, and hoisting the fp64 constants of atan / sincos out of the tick loop shortens the tick; every other kernel
-# and the C ABI are the object without it (SHIPSIM_TU 1).
-OBJECTS = {"sacfused": [["-DSACF_TU=1", "-mllvm", "-amdgpu-sched-strategy=max-ilp"], ["-DSACF_TU=2"]],
-           "shipsim": [["-DSHIPSIM_TU=1", "-mllvm", "-disable-machine-licm"], ["-DSHIPSIM_TU=2"]]}
+# so the widths up to 384 (and the C ABI) are one object with it and the two widest another without: two objects of
+# the same source (sac_kernels.hip SACF_TU).
+# shipsim: every kernel but the C2 three-wave one, and the C ABI, are shipsim_kernels.hip, built without machine LICM
+# (above); the C2 three-wave kernel is a source of its own that keeps it — its loops have registers to spare, and
+# hoisting the fp64 constants of atan / sincos out of the tick loop shortens the tick.
+OBJECTS = {"sacfused": [("ast_sac_amd/csrc/sac_kernels.hip", ["-DSACF_TU=1", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
+                        ("ast_sac_amd/csrc/sac_kernels.hip", ["-DSACF_TU=2"])],
+           "shipsim": [("ast_sac_amd/csrc/shipsim_kernels.hip", ["-mllvm", "-disable-machine-licm"]),
+                       ("ast_sac_amd/csrc/shipsim_c2_pipe.hip", [])]}
+
+
+def lib_objects(lib):
+    """The objects the library is linked from: (source file relative to the repository root, its flag set)."""
+    return [(src, LIB_FLAGS[lib] + extra) for src, extra in OBJECTS[lib]]
 
 
 def lib_flag_sets(lib):
-    """The flag sets the library is compiled with: one per object (one set for a single-object library)."""
-    return [LIB_FLAGS[lib] + extra for extra in OBJECTS.get(lib, [[]])]
+    """The flag sets the library is compiled with, one per object."""
+    return [flags for _, flags in lib_objects(lib)]
 
 
 def source_hash(lib):

@@ -1,5 +1,9 @@
 // shipsim_kernels.hip — HIP kernels (gfx950) + C ABI (include/shipsim.h) of the batched
-// ship-in-transit simulator -> ast_sac_amd/lib/libshipsim.so, linked from two objects of this file (SHIPSIM_TU below).
+// ship-in-transit simulator -> ast_sac_amd/lib/libshipsim.so, linked from this file's object and
+// shipsim_c2_pipe.hip's (ast_sac_amd/build_hash.py OBJECTS: this one is built without machine-level LICM, the tick
+// loops' constants are rematerialised rather than held in registers).
+// The shared device state is shipsim_state.hpp, the ship model shipsim_device.hpp (types: shipsim_types.hpp); the host
+// halves that need no device are the shipsim_*_host.hpp headers, shipsim_create's being shipsim_config_host.hpp.
 //
 // Kernels
 //   init_kernel    : state as constructed (ShipModelAST/SimpleShipModel.__init__, controllers,
@@ -8,7 +12,7 @@
 //   ast_step_kernel: MultiShipRLEnv.step (env.py:624-773) — event-driven: each env ticks
 //                    (_step :563-622) until its decision point (RoA + 1 tick) or done
 //   single_tick_kernel: C2 single-ship loop body (run_colav/run_simplified_model.py:248-249 shape)
-//   single_tick_pipe_kernel: the same for the simplified machinery, three waves per 64 ships
+//   single_tick_pipe_kernel: the same for the simplified machinery, three waves per 64 ships (shipsim_c2_pipe.hip)
 //   fork_gather_kernel: shipsim_fork — env i takes env src_env[i]'s share of every column of the state block
 #include <hip/hip_runtime.h>
 
@@ -23,121 +27,19 @@
 
 #include "shipsim.h"
 #include "shipsim_device.hpp"
+#include "shipsim_state.hpp"         // DevState, ConstBuf, load_ship / store_ship, stage_consts
+#include "shipsim_config_host.hpp"   // shipsim_default_config and shipsim_create's host half
 #include "shipsim_launch_host.hpp"   // the list of step kernels and the choice among them
 #include "shipsim_weather_host.hpp"  // shipsim_set_weather's host half
 #include "shipsim_state_host.hpp"    // the state block as a table of columns (snapshot / restore / fork)
 
 #include "shipsim_diag.hpp"  // diagnostics / ablation hooks (none in the product build)
 
-
 using namespace shipsim;
 static_assert(kWeatherCols == weather_host::kCols && WX_WIND_SPEED == weather_host::kWindSpeed &&
                   WX_WIND_SIN == weather_host::kWindSin && WX_WIND_COS == weather_host::kWindCos &&
                   WX_VC_N == weather_host::kCurrentN && WX_VC_E == weather_host::kCurrentE,
               "the weather array's columns: device and host agree");
-
-// Translation-unit role (ast_sac_amd/build_hash.py OBJECTS):
-//   SHIPSIM_TU 1: every kernel but single_tick_pipe_kernel, and the C ABI — built without machine-level LICM (the
-//                 tick loops' constants are rematerialised rather than held in registers: DESIGN.md §7a)
-//   SHIPSIM_TU 2: single_tick_pipe_kernel and its launch only — with LICM: its three short loops have registers to
-//                 spare, and the fp64 constants of atan / sincos are hoisted out of the tick loop
-//   SHIPSIM_TU 0: everything in one object (diagnostics and register-report builds)
-#ifndef SHIPSIM_TU
-#define SHIPSIM_TU 0
-#endif
-// (defined with single_tick_pipe_kernel, in the SHIPSIM_TU 2 object of the product build)
-void shipsim_c2_pipe_launch(int blocks, hipStream_t st, const Params& P, const struct DevState& S,
-                            const struct ConstBuf& K, int k);
-
-// ---------------------------------------------------------------------------------------------
-// device state (SoA). Ship arrays are indexed q = env * n_ships + ship (lane order).
-// ---------------------------------------------------------------------------------------------
-struct DevState {
-  // One device block; every array lives at base + (index * stride). Keeping the table as one base
-  // pointer + strides (instead of ~40 pointers) keeps it out of the SGPR budget of the big kernel.
-  char* base;
-  int64_t ship_stride;   // bytes of one [env][ship] array (doubles)
-  int64_t route_stride;  // bytes of one [env][ship][kMaxRoute] route array
-  int64_t env_stride;    // bytes of one per-env array (sized for the widest: 8 floats)
-  int64_t env_off;       // start of the per-env arrays
-  __host__ __device__ double* f(int k) const { return (double*)(base + k * ship_stride); }
-  __host__ __device__ int32_t* next_wpt() const { return (int32_t*)(base + 19 * ship_stride); }
-  __host__ __device__ int32_t* stop() const { return (int32_t*)(base + 20 * ship_stride); }
-  __host__ __device__ int32_t* n_route() const { return (int32_t*)(base + 21 * ship_stride); }
-  __host__ __device__ double* route_n() const { return (double*)(base + 22 * ship_stride); }
-  __host__ __device__ double* route_e() const { return (double*)(base + 22 * ship_stride + route_stride); }
-  __host__ __device__ char* ev(int k) const { return base + env_off + k * env_stride; }
-  __host__ __device__ int32_t* sampling_count() const { return (int32_t*)ev(0); }
-  __host__ __device__ double* travel_dist() const { return (double*)ev(1); }
-  __host__ __device__ double* travel_time() const { return (double*)ev(2); }
-  __host__ __device__ double* acc() const { return (double*)ev(3); }
-  __host__ __device__ double* n_base() const { return (double*)ev(4); }
-  __host__ __device__ double* e_base() const { return (double*)ev(5); }
-  __host__ __device__ double* p_last() const { return (double*)ev(6); }
-  __host__ __device__ double* chi_last() const { return (double*)ev(7); }
-  __host__ __device__ double* mach_dt() const { return (double*)ev(8); }
-  __host__ __device__ float* states4() const { return (float*)ev(9); }      // [env][4] self.states (simple collav)
-  __host__ __device__ float* next_obs8() const { return (float*)ev(10); }   // [env][8] self.next_observations
-  __host__ __device__ uint32_t* snap_bits() const { return (uint32_t*)ev(11); }
-  __host__ __device__ int32_t* was_reset() const { return (int32_t*)ev(12); }
-  __host__ __device__ int32_t* dec_flags() const { return (int32_t*)ev(13); }  // DF_* (sliced stepping)
-  __host__ __device__ double* legacy_states() const { return (double*)ev(14); }  // [env][4] legacy self.states
-  __host__ __device__ int32_t* legacy_flags() const { return (int32_t*)ev(15); }  // 1: still the f32 initial_states
-  __host__ __device__ int32_t* dec_ticks() const { return (int32_t*)ev(16); }  // ticks of the decision in progress
-  // the decision in progress as the stream logs it (SHIPSIM_DL_ACTION / _OBS0): its action, the observation it
-  // was chosen from
-  __host__ __device__ float* dec_action() const { return (float*)ev(17); }
-  __host__ __device__ float* dec_obs0() const { return (float*)ev(18); }  // [env][8]
-  int32_t* nonfinite;  // device counter: envs flagged SHIPSIM_EV_NONFINITE (read by shipsim_synchronize)
-  static constexpr int kEnvArrays = 19;
-  static constexpr int kShipArrays = 22;
-};
-// shipsim_fork moves the columns of state_host::table(): an array added here gets its row there
-static_assert(DevState::kEnvArrays == state_host::kEnvArrays && DevState::kShipArrays == state_host::kShipArrays &&
-                  kMaxRoute * sizeof(double) == state_host::kRouteSlotBytes,
-              "DevState and the column table (shipsim_state_host.hpp) list the same arrays");
-// dec_flags bits (per env, persistent across calls)
-#define DF_AWAITING 1
-#define DF_HAVE_IW 2
-#define DF_PHASE_SHIFT 2
-
-enum { SF_N = 0, SF_E, SF_YAW, SF_U, SF_V, SF_R, SF_OMEGA, SF_TIME, SF_ECT, SF_ECT_INT, SF_HDG_EI, SF_HDG_PREV,
-       SF_SPD_A, SF_SPD_B, SF_RUDDER, SF_THRUST, SF_LOG_ECT, SF_LOG_N, SF_LOG_E };
-
-struct ConstBuf {
-  // edges [SHIPSIM_MAX_VERTS] | boxes [SHIPSIM_MAX_POLYS] | config routes n/e [MAX_SHIPS][kMaxRoute] each
-  // | ShipConst [MAX_SHIPS] | map grid: cell edge masks [gny][gnx] uint64 | cell containment flags [gny][gnx] uint8
-  // | (8-B aligned) cell edge masks split by bit rank mod 8 [gny][gnx][8] uint64
-  const char* base;
-  int32_t n_edges;
-  int32_t gnx, gny;            // grid cells (0 = no grid: every query runs over the full map)
-  double gx0, gy0, ginv;       // grid origin (east, north) and 1 / cell size
-  const uint64_t* grid_mask;   // edges whose distance to the (slightly enlarged) cell is <= kGroundReach
-  const uint8_t* grid_flag;    // GRID_OUT: cell entirely outside every polygon, GRID_IN: inside one, GRID_MIXED
-  const uint64_t* grid_part;   // [cell][8]: the cell's mask split by bit rank mod 8 (sub-lane shares, no bit skipping)
-  __host__ __device__ const Edge* edges() const { return (const Edge*)base; }
-  __host__ __device__ const PolyBox* boxes() const { return (const PolyBox*)(base + sizeof(Edge) * SHIPSIM_MAX_VERTS); }
-  __host__ __device__ const double* cfg_route_n() const {
-    return (const double*)(base + sizeof(Edge) * SHIPSIM_MAX_VERTS + sizeof(PolyBox) * SHIPSIM_MAX_POLYS);
-  }
-  __host__ __device__ const double* cfg_route_e() const { return cfg_route_n() + SHIPSIM_MAX_SHIPS * kMaxRoute; }
-  // per-ship constants (host make_ship_const), [ship] for the 1 + K ships of an env
-  static constexpr size_t kShipsOff = sizeof(Edge) * SHIPSIM_MAX_VERTS + sizeof(PolyBox) * SHIPSIM_MAX_POLYS +
-                                      sizeof(double) * 2 * SHIPSIM_MAX_SHIPS * kMaxRoute;
-  __host__ __device__ const ShipConst* ships() const { return (const ShipConst*)(base + kShipsOff); }
-  static constexpr size_t kBytes = kShipsOff + sizeof(ShipConst) * SHIPSIM_MAX_SHIPS;
-  // grid cell of (north, east), or -1 outside the grid / no grid / non-finite position
-  __device__ __forceinline__ int cell(double n, double e) const { return grid_cell(*this, n, e); }
-};
-#define GRID_OUT 0
-#define GRID_IN 1
-#define GRID_MIXED 2
-
-// The ground-distance reward terms only use the coastline distance when it is <= 1000 m
-// (reward_function.py:109-117: test_ship_grounding_reward / obs_ship_grounding_reward clip at 1 km),
-// so a cell only needs the edges that can come within 1000 m of it: the min over that subset equals
-// the min over all edges whenever the true min is <= 1000 m, and is > 1000 m (or +inf) otherwise.
-constexpr double kGroundReach = 1000.0;
 
 // Trajectory record (shipsim_set_trajectory): simulation_results rows per ship, RewardTracker rows per
 // env. Row t of a ship is its t-th store_simulation_data since reset (row 0 = init_step); env row t is
@@ -156,47 +58,6 @@ struct Traj {
   }
 };
 
-__device__ __forceinline__ void load_ship(const DevState& S, int q, Ship& s) {
-  s.n = S.f(SF_N)[q]; s.e = S.f(SF_E)[q]; s.yaw = S.f(SF_YAW)[q];
-  s.u = S.f(SF_U)[q]; s.v = S.f(SF_V)[q]; s.r = S.f(SF_R)[q];
-  s.omega = S.f(SF_OMEGA)[q]; s.time = S.f(SF_TIME)[q];
-  s.e_ct = S.f(SF_ECT)[q]; s.e_ct_int = S.f(SF_ECT_INT)[q];
-  s.hdg_ei = S.f(SF_HDG_EI)[q]; s.hdg_prev = S.f(SF_HDG_PREV)[q];
-  s.spd_a = S.f(SF_SPD_A)[q]; s.spd_b = S.f(SF_SPD_B)[q];
-  s.log_rudder = S.f(SF_RUDDER)[q]; s.log_thrust = S.f(SF_THRUST)[q]; s.log_ect = S.f(SF_LOG_ECT)[q];
-  s.log_n = S.f(SF_LOG_N)[q]; s.log_e = S.f(SF_LOG_E)[q];
-  s.next_wpt = S.next_wpt()[q]; s.stop = S.stop()[q]; s.n_route = S.n_route()[q];
-  load_segment(s, S.route_n() + (size_t)q * kMaxRoute, S.route_e() + (size_t)q * kMaxRoute);
-}
-__device__ __forceinline__ void store_ship(const DevState& S, int q, const Ship& s) {
-  S.f(SF_N)[q] = s.n; S.f(SF_E)[q] = s.e; S.f(SF_YAW)[q] = s.yaw;
-  S.f(SF_U)[q] = s.u; S.f(SF_V)[q] = s.v; S.f(SF_R)[q] = s.r;
-  S.f(SF_OMEGA)[q] = s.omega; S.f(SF_TIME)[q] = s.time;
-  S.f(SF_ECT)[q] = s.e_ct; S.f(SF_ECT_INT)[q] = s.e_ct_int;
-  S.f(SF_HDG_EI)[q] = s.hdg_ei; S.f(SF_HDG_PREV)[q] = s.hdg_prev;
-  S.f(SF_SPD_A)[q] = s.spd_a; S.f(SF_SPD_B)[q] = s.spd_b;
-  S.f(SF_RUDDER)[q] = s.log_rudder; S.f(SF_THRUST)[q] = s.log_thrust; S.f(SF_LOG_ECT)[q] = s.log_ect;
-  S.f(SF_LOG_N)[q] = s.log_n; S.f(SF_LOG_E)[q] = s.log_e;
-  S.next_wpt()[q] = s.next_wpt; S.stop()[q] = s.stop; S.n_route()[q] = s.n_route;
-}
-
-// per-block LDS copy of the ships' ShipConst (lanes of one ship read one address)
-// (and the reciprocals div_by uses, formed here on the device: the bits of the division sequence's own)
-__device__ __forceinline__ const ShipConst* stage_consts(const ConstBuf& K, ShipConst* lds, int n_ships, double dt) {
-  const int nwords = (int)(sizeof(ShipConst) * n_ships / sizeof(double));
-  const double* src = reinterpret_cast<const double*>(K.ships());
-  double* dst = reinterpret_cast<double*>(lds);
-  for (int i = threadIdx.x; i < nwords; i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
-  if ((int)threadIdx.x < n_ships) {
-    ShipConst& c = lds[threadIdx.x];
-    c.rcp_r_me = div_rcp(c.r_me); c.rcp_r_hsg = div_rcp(c.r_hsg); c.rcp_jp = div_rcp(c.jp); c.rcp_dt = div_rcp(dt);
-  }
-  __syncthreads();
-  return lds;
-}
-
-#if SHIPSIM_TU != 2
 // control half of one ship tick: autopilot -> speed control -> (simple collav) -> store
 // (env.py test_step :389-433 / obs_step :481-512 / init_step :309-339); returns (ctrl, rudder)
 // PRE: (pre_q, pre_e) = los_q at (s.n, s.e) on the current segment, evaluated earlier in the tick; used unless the
@@ -322,611 +183,7 @@ __device__ __forceinline__ void record_last(const Traj& T, int q, int t, double 
   row[SHIPSIM_TS_TIME_LIST] = time_list;
 }
 
-// ---------------------------------------------------------------------------------------------
-// SBMPC (sbmpc.py:113-298), wave-cooperative: each requesting env's 7 x 4 scenarios are spread
-// over 28 lanes of a half-wave; two envs are served per pass.
-// ---------------------------------------------------------------------------------------------
-struct SbIn {
-  double u_d, chi_d, os_x, os_y, os_v, ob_x, ob_y, ob_psi, ob_u, ob_v, obs_l, obs_w, p_last, chi_last;
-  double ob_so, ob_co;  // sin / cos(ob_psi): the AST kernels pass the obstacle ship's carried sin/cos(yaw)
-};
-// sin/cos(ob_psi) of a request built from its heading alone
-__device__ __forceinline__ void sb_set_heading_trig(SbIn& q) { sincos(q.ob_psi, &q.ob_so, &q.ob_co); }
-
-// a lane value the compiler must re-derive after this point (loads indexed by it cannot be hoisted)
-__device__ __forceinline__ int opaque_v(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-// a wave-uniform value the compiler must re-derive after this point (comparisons on it cannot be hoisted)
-__device__ __forceinline__ int opaque_s(int x) {
-  asm volatile("" : "+s"(x));
-  return x;
-}
-// opaque_v where OPQ (the kernels whose allocation otherwise spills the lane masks derived from x), x as is
-// elsewhere (there the recomputation costs more than the held mask)
-template <bool OPQ>
-__device__ __forceinline__ int opaque_if(int x) {
-  if constexpr (OPQ) return opaque_v(x);
-  return x;
-}
-
-__device__ __forceinline__ double shfl_d(double x, int src) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __shfl(lo, src, 64);
-  hi = __shfl(hi, src, 64);
-  return __hiloint2double(hi, lo);
-}
-
-constexpr double kCosPhiAh = 0.36650122672429719;  // cos(68.5°) (only used against a 1e-9 band)
-constexpr double kSinPhiAh = 0.93041756798202460;  // sin(68.5°)
-
-// sqrt(a) < c and sqrt(a) <= c (c > 0) decided on a against c², except within a relative 1e-12 of
-// it where the correctly rounded square root itself decides: the reference's boolean, without the
-// ~20-instruction f64 sqrt on every tick (NaN compares false either way)
-__device__ __forceinline__ bool sqrt_lt(double a, double c) {
-  const double c2 = c * c;
-  if (a < c2 * (1.0 - 1e-12)) return true;
-  if (!(a <= c2 * (1.0 + 1e-12))) return false;
-  return sqrt(a) < c;
-}
-__device__ __forceinline__ bool sqrt_le(double a, double c) {
-  const double c2 = c * c;
-  if (a < c2 * (1.0 - 1e-12)) return true;
-  if (!(a <= c2 * (1.0 + 1e-12))) return false;
-  return sqrt(a) <= c;
-}
-
-// (d_safe / dist) ** Q_ with Q_ = 4 (sbmpc.py:262): x² = h + l and h² = h2 + e exactly (fma), so
-// h2 + (e + (2hl + l²)) carries ~100 bits into its one final rounding — the correctly rounded x⁴, which
-// is glibc's pow(x, 4.0) except where that pow's last 0.02 ulp decides (85 per 10⁵ random d_safe / dist
-// in (0.9, 1000]) — in 11 VALU instructions instead of the general pow's 214. An infinite x⁴ (dist -> 0)
-// is returned as is.
-__device__ __forceinline__ double pow4(double x) {
-  const double h = x * x, l = fma(x, x, -h);
-  const double h2 = h * h;
-  if (!(h2 < INFINITY)) return h2;
-  const double e = fma(h, h, -h2);
-  return h2 + (e + (2.0 * h * l + l * l));
-}
-
-// Per-sample collision cost H0 = C·R of sbmpc.py:205-289 (KAPPA_ = 0) for one prediction sample with
-// obstacle-minus-own-ship offset (d0, d1); (ss, cs, sv) are the own ship's sin/cos(psi_) and sway
-// at that sample. R and C stay 0 unless dist < d_safe_i <= max_d_safe, so the sector geometry (atan2,
-// wrap, norms) is only evaluated there; identical results to the reference's `dist < d_close` block.
-__device__ __forceinline__ double sbmpc_sample_cost(const SbIn& in, double so, double co, double vo0, double vo1,
-                                                    double no, double t, double d0, double d1, double d2s,
-                                                    double ss, double cs, double ud, double sv, double max_d_safe,
-                                                    double lim2, double cos_ot) {
-  const double os_l = 25.0, d_safe = 1000.0, d_close = 2000.0;
-  const double PHI_AH = 68.5 * (kPi / 180.0), PHI_OT = 68.5 * (kPi / 180.0);
-  if (!(d2s < lim2)) return 0.0;  // d2s >= lim2 already implies sqrt(d2s) >= max_d_safe
-  const double dist = sqrt(d2s);
-  if (!(dist < d_close && dist < max_d_safe)) return 0.0;
-  double vs0 = -ss * ud + cs * sv;
-  double vs1 = cs * ud + ss * sv;
-  // sector of phi_o = wrap(atan2(-d1, -d0) - psi_o + pi/2) against PHI_AH == PHI_OT = θ: e is
-  // (-d0, -d1) rotated by pi/2 - psi_o, so phi_o = angle(e); phi_o > θ <=> sin(angle(e) - θ) >= 0
-  // and e_y > 0. Within 1e-9 rad of a decision boundary the reference expression is evaluated.
-  const double ex = so * (-d0) - co * (-d1), ey = co * (-d0) + so * (-d1);
-  const double cr = kCosPhiAh * ey - kSinPhiAh * ex;
-  int sector;  // 0: phi_o < PHI_AH, 1: phi_o > PHI_OT, 2: equal
-  if (fabs(cr) > 1e-9 * dist && fabs(ey) > 1e-9 * dist) {
-    sector = (cr >= 0 && ey > 0) ? 1 : 0;
-  } else {
-    const double phi_o = wrap_pmpi(atan2(-d1, -d0) - in.ob_psi + kPi / 2);
-    sector = (phi_o < PHI_AH) ? 0 : ((phi_o > PHI_OT) ? 1 : 2);
-  }
-  double d_safe_i;
-  if (sector == 0) d_safe_i = d_safe + in.obs_l / 2;
-  else if (sector == 1) d_safe_i = 0.5 * d_safe + in.obs_l / 2;
-  else d_safe_i = d_safe + in.obs_w / 2;
-  double dot = vs0 * vo0 + vs1 * vo1;
-  double ns = sqrt(vs0 * vs0 + vs1 * vs1);
-  if (dot > cos_ot * ns * no && ns > no) d_safe_i = d_safe + os_l / 2 + in.obs_l / 2;
-  if (!(dist < d_safe_i)) return 0.0;
-  const double R = (1 / fabs(t - 0.0)) * pow4(d_safe / dist);  // pow(|t|, 1.0) == |t| exactly
-  const double k_coll = 1e-6 * os_l * in.obs_l;
-  const double w0 = vs0 - vo0, w1 = vs1 - vo1;
-  const double nrm = sqrt(w0 * w0 + w1 * w1);
-  const double C = k_coll * (nrm * nrm);
-  return C * R + 0.0 * 0;
-}
-
-// sbmpc.py:190-298 cost_func for one (Chi_ca, P_ca) scenario, sample by sample as the reference.
-// Kept as the exact fallback of sbmpc_scenario_cost (near-ties between samples).
-__device__ __forceinline__ double sbmpc_scenario_cost_direct(const SbIn& in, int n_samp, double DT, double ud,
-                                                          double sp, double cp, double sp0, double cp0, double so,
-                                                          double co, double vo0, double vo1, double no,
-                                                          double max_d_safe, double lim2, double cos_ot, double H2) {
-  const double r11 = -so, r12 = co, r21 = co, r22 = so;
-  const double q11 = -sp, q12 = cp, q21 = cp, q22 = sp;
-  double ox = in.ob_x, oy = in.ob_y, sx = in.os_x, sy = in.os_y, sv = in.os_v;
-  double H1 = 0, t = 0;
-  for (int i = 0; i < n_samp; ++i) {
-    if (i > 0) {
-      ox = ox + (r11 * in.ob_u + r12 * in.ob_v) * DT;
-      oy = oy + (r21 * in.ob_u + r22 * in.ob_v) * DT;
-      sx = sx + DT * (q11 * ud + q12 * sv);
-      sy = sy + DT * (q21 * ud + q22 * sv);
-      sv = 0.0;
-    }
-    t += DT;
-    const double d0 = ox - sx, d1 = oy - sy;
-    const double H0 = sbmpc_sample_cost(in, so, co, vo0, vo1, no, t, d0, d1, d0 * d0 + d1 * d1, (i == 0) ? sp0 : sp,
-                                        (i == 0) ? cp0 : cp, ud, sv, max_d_safe, lim2, cos_ot);
-    if (H0 > H1) H1 = H0;
-  }
-  return H1 + H2;
-}
-
-
-// SBMPCParams.P_ca_ = [0.4, 0.6, 0.8, 1.0] (sbmpc.py:36) by selects: a per-lane indexed constant array would be
-// a memory load on the scenario's critical path
-__device__ __forceinline__ double p_ca_of(int jp) {
-  return jp == 0 ? 0.4 : (jp == 1 ? 0.6 : (jp == 2 ? 0.8 : 1.0));
-}
-
-// the scenario's own terms of the cost (sbmpc.py:200-214: P_ca, Chi_ca and their changes); the whole
-// cost when no obstacle sample comes within max_d_safe
-__device__ __forceinline__ double sbmpc_h2(const SbIn& in, int ichi, int jp) {
-  const double P_ca = p_ca_of(jp);
-  const double Chi_ca = (-30.0 + 10.0 * ichi) * (kPi / 180.0);
-  const double dChi0 = Chi_ca - in.chi_last;
-  return 25 * (1 - P_ca) + 30 * (Chi_ca * Chi_ca) + 20 * fabs(in.p_last - P_ca) +
-         ((dChi0 > 0) ? 20 * dChi0 * dChi0 : (dChi0 < 0 ? 30 * dChi0 * dChi0 : 0));
-}
-
-// No scenario can bring this obstacle within max_d_safe over the horizon: the distance now minus the
-// most either ship can travel (own ship: sample 0 at its current sway, then straight at <= u_d; the
-// obstacle: straight at its speed) stays beyond max_d_safe with a 1 m margin (the incremental
-// predictions round at ~1e-12 relative). Then every scenario's cost for it is exactly sbmpc_h2.
-__device__ __forceinline__ bool sbmpc_far(const SbIn& in, int n_samp, double DT) {
-  const double os_l = 25.0, d_safe = 1000.0;
-  const double max_d_safe = py_max(py_max(d_safe + in.obs_l / 2, 0.5 * d_safe + in.obs_l / 2),
-                                   py_max(d_safe + in.obs_w / 2, d_safe + os_l / 2 + in.obs_l / 2));
-  const double ex = in.ob_x - in.os_x, ey = in.ob_y - in.os_y;
-  const double own = DT * sqrt(in.u_d * in.u_d + in.os_v * in.os_v) + (n_samp - 2 > 0 ? n_samp - 2 : 0) * DT * in.u_d;
-  const double obs = (n_samp - 1) * DT * sqrt(in.ob_u * in.ob_u + in.ob_v * in.ob_v);
-  const double lim = max_d_safe + 1.0 + own + obs;
-  return ex * ex + ey * ey > lim * lim;
-}
-
-// running state of a scenario's horizon: best (s1 at time t1, squared distance q1) and runner-up s2 of the
-// ranking t·d², and whether any in-range sample sat within a rounding band of a decision (unc)
-struct HzBest {
-  double s1, s2, t1, q1;
-  bool unc;
-};
-struct HzConst {
-  double so, co, ovr2, ot2, ah2, cl2;  // obstacle heading sin/cos, squared thresholds
-  bool ovr;                            // the overtaking override of d_safe_i holds for every sample
-};
-// one horizon sample (time tt, offset (d0, d1), d2s = |.|²) into the running state; inr: the sample is within
-// max_d_safe (one beyond it contributes nothing and flags nothing). Branch-free (& | on bools).
-__device__ __forceinline__ void hz_sample(HzBest& h, const HzConst c, double tt, double d0, double d1, double d2s,
-                                          bool inr) {
-  constexpr double kEps = 1e-12;
-  // sector of phi_o (see sbmpc_sample_cost): overtaking sector iff cr >= 0 and ey > 0
-  const double ex = c.so * (-d0) - c.co * (-d1), ey = c.co * (-d0) + c.so * (-d1);
-  const double cr = kCosPhiAh * ey - kSinPhiAh * ex;
-  const bool sec_ok = (cr * cr > 1e-18 * d2s) & (ey * ey > 1e-18 * d2s);
-  const double D2 = c.ovr ? c.ovr2 : (((cr >= 0) & (ey > 0)) ? c.ot2 : c.ah2);
-  const bool member = inr & (d2s < D2 * (1.0 - kEps)) & (d2s < c.cl2 * (1.0 - kEps));
-  h.unc = h.unc | (inr & (((!c.ovr) & (!sec_ok)) | (fabs(d2s - D2) <= kEps * D2) | (fabs(d2s - c.cl2) <= kEps * c.cl2)));
-  const double sc = member ? tt * d2s * d2s : INFINITY;
-  const bool lt1 = sc < h.s1;
-  h.s2 = fmin(h.s2, fmax(h.s1, sc));  // runner-up: the old best if sc takes the lead, else min(s2, sc)
-  h.t1 = lt1 ? tt : h.t1;
-  h.q1 = lt1 ? d2s : h.q1;
-  h.s1 = fmin(h.s1, sc);
-}
-
-// part -1: the whole horizon on this lane. part 0 / 1: this lane and its partner (lane ^ 32: the same scenario of the
-// same request) split the horizon's sample loop — part 0 takes the samples before i_split, part 1 the rest — and merge
-// their running bests (every other step is computed by both; the result is the same bits as part -1)
-__device__ double sbmpc_scenario_cost(const SbIn& in, int n_samp, double DT, int ichi, int jp, int part = -1) {
-  SB_TIMER;
-  const double os_l = 25.0;  // ShipLinearModel default length (sbmpc_misc.py:86, Q7)
-  const double d_safe = 1000.0, d_close = 2000.0;
-  // np.cos(np.deg2rad(PHI_OT_)) — PHI_OT_ is already in radians (sbmpc.py:248): a constant, taken
-  // as the correctly rounded double of cos(68.5·(π/180)²) (NumPy and glibc agree on it)
-  constexpr double cos_ot = 0.9997823068017366;
-  const double max_d_safe = py_max(py_max(d_safe + in.obs_l / 2, 0.5 * d_safe + in.obs_l / 2),
-                                   py_max(d_safe + in.obs_w / 2, d_safe + os_l / 2 + in.obs_l / 2));
-  const double CHI_DEG = -30.0 + 10.0 * ichi;
-  const double P_ca = p_ca_of(jp);
-  const double Chi_ca = CHI_DEG * (kPi / 180.0);
-  const double ud = in.u_d * P_ca;
-  const double psi_d = in.chi_d + Chi_ca;
-  // Obstacle trajectory (sbmpc_misc.py:65-83) and linear_pred (:103-123), advanced incrementally
-  // the obstacle heading's sin/cos come with the request (ob_so, ob_co): the same values as
-  // sincos(in.ob_psi) — in the AST kernels they are the obstacle ship's own carried sin/cos(yaw) with
-  // ob_psi = -yaw, and the device sin is odd and cos even (both reduce |x|), so nothing is recomputed
-  // per scenario
-  const double so = in.ob_so, co = in.ob_co;
-  const double r11 = -so, r12 = co, r21 = co, r22 = so;
-  const double vo0 = -so * in.ob_u + co * in.ob_v;  // rot2d(obstacle.psi_, [u, v])
-  const double vo1 = co * in.ob_u + so * in.ob_v;
-  const double no = sqrt(vo0 * vo0 + vo1 * vo1);
-  double sp, cp;
-  sincos(psi_d, &sp, &cp);
-  const double q11 = -sp, q12 = cp, q21 = cp, q22 = sp;
-  double sp0 = sp, cp0 = cp;
-  const double psi_w = wrap_pmpi(psi_d);
-  if (psi_w != psi_d) sincos(psi_w, &sp0, &cp0);
-  const double H2 = sbmpc_h2(in, ichi, jp);
-  int i_last = n_samp - 1;  // (set by the skip test below)
-  int i_first = 1;          // first sample that can be within range (ditto; only places the split)
-  int i_past = n_samp + 1;  // first sample past the closest approach, with a one-sample margin (ditto)
-  // Exact skip of the horizon loop: H0 can only be non-zero at samples with dist < max_d_safe.
-  // After sample 0 both predictions are straight lines (the own ship's sway is zeroed after the
-  // first step), so the relative position is P1 + k·W, k = 0..n_samp-2; if its continuous minimum
-  // (and sample 0) stays above max_d_safe by a margin far beyond the rounding of the incremental
-  // update below, every sample's H0 is 0 and the cost is H2 alone.
-  {
-    const double vox = r11 * in.ob_u + r12 * in.ob_v, voy = r21 * in.ob_u + r22 * in.ob_v;
-    const double e0x = in.ob_x - in.os_x, e0y = in.ob_y - in.os_y;
-    const double p1x = (in.ob_x + vox * DT) - (in.os_x + DT * (q11 * ud + q12 * in.os_v));
-    const double p1y = (in.ob_y + voy * DT) - (in.os_y + DT * (q21 * ud + q22 * in.os_v));
-    const double wx = (vox - q11 * ud) * DT, wy = (voy - q21 * ud) * DT;
-    const double ww = wx * wx + wy * wy;
-    const double iww = ww > 0 ? 1.0 / ww : 0.0;  // (k and j2 below only place bounds with margins)
-    double k = ww > 0 ? -(p1x * wx + p1y * wy) * iww : 0.0;
-    k = k < 0 ? 0 : (k > n_samp - 2 ? n_samp - 2 : k);
-    const double mx = p1x + k * wx, my = p1y + k * wy;
-    const double lim = max_d_safe + 1e-3;
-    SB_MARK(0);
-    if (e0x * e0x + e0y * e0y > lim * lim && mx * mx + my * my > lim * lim) return 0.0 + H2;
-    // Last sample that can still be within max_d_safe: |P1 + j·W| is convex in j, so past the larger
-    // root j2 of |P1 + j·W| = lim every later sample stays out of range (the incremental positions
-    // below differ from this closed form by ~1e-10 m, far inside the 1e-3 m of lim). Sample i = j + 1.
-    const double b = p1x * wx + p1y * wy, cq = p1x * p1x + p1y * p1y - lim * lim;
-    const double disc = b * b - ww * cq;
-    const double j2 = (ww > 0 && disc >= 0) ? (-b + sqrt(disc)) * iww : (double)n_samp;
-    i_last = (j2 < (double)(n_samp - 2)) ? (int)floor(j2) + 2 : n_samp - 1;
-    const double j1 = (ww > 0 && disc >= 0) ? (-b - sqrt(disc)) * iww : 0.0;
-    i_first = (j1 > 1.0) ? (int)fmin(floor(j1), (double)(n_samp - 1)) : 1;
-    // Past the continuous minimum k of |P1 + j·W| both t and the distance grow, so the ranking t·d⁴ grows
-    // sample by sample: once a sample there ranks beyond the best so far by more than the runner-up band,
-    // no later sample can win or tie (and a later sample's flags cannot change the result). Sample i = j + 1;
-    // k is clamped to the horizon, so a minimum at its end never stops the loop.
-    i_past = (int)ceil(k) + 3;
-  }
-  const double lim2 = (max_d_safe * (1.0 + 1e-9)) * (max_d_safe * (1.0 + 1e-9));
-  // Sample 0 (own ship at wrap(psi_d) with its current sway) exactly as the reference.
-  const double e0x = in.ob_x - in.os_x, e0y = in.ob_y - in.os_y;
-  double H1 = 0;
-  {
-    const double H0 = sbmpc_sample_cost(in, so, co, vo0, vo1, no, DT, e0x, e0y, e0x * e0x + e0y * e0y, sp0, cp0, ud,
-                                        in.os_v, max_d_safe, lim2, cos_ot);
-    if (H0 > H1) H1 = H0;
-  }
-  SB_MARK(1);
-  // Samples 1..n-1: the own ship's velocity is constant (sway zeroed), so C and the overtaking
-  // override of d_safe_i are sample-independent, and H0 = C·R with R = d_safe^4 / (t·dist^4).
-  // max_i fl(C·R_i) = fl(C·max_i R_i) (rounding is monotone), so only the sample with the largest
-  // R needs the exact pow: members are ranked by s = t·d2s² (within ~1e-14 of the exact ordering);
-  // a runner-up within 1e-10 of the best sends the scenario to the sample-by-sample evaluation.
-  const double vs0 = -sp * ud + cp * 0.0, vs1 = cp * ud + sp * 0.0;
-  const double dot1 = vs0 * vo0 + vs1 * vo1;
-  const double ns1 = sqrt(vs0 * vs0 + vs1 * vs1);
-  const bool ovr = dot1 > cos_ot * ns1 * no && ns1 > no;
-  const double ds_ah = d_safe + in.obs_l / 2, ds_ot = 0.5 * d_safe + in.obs_l / 2;  // :239-242
-  const double ds_ovr = d_safe + os_l / 2 + in.obs_l / 2;
-  // Branch-free horizon: membership dist < d_safe_i (and < d_close) is decided on d2s against the
-  // squared thresholds; a sample within 1e-12 of a threshold, or whose sector is within 1e-9 of
-  // the PHI_AH / PHI_OT boundary, marks the scenario `unc` and it is re-evaluated sample by sample.
-  constexpr double kEps = 1e-12;
-  const double ah2 = ds_ah * ds_ah, ot2 = ds_ot * ds_ot, ovr2 = ds_ovr * ds_ovr, cl2 = d_close * d_close;
-  // position increments: the obstacle's are constant, the own ship's use its sway at sample 1
-  // only (linear_pred zeroes v after the first step)
-  const double dox = (r11 * in.ob_u + r12 * in.ob_v) * DT, doy = (r21 * in.ob_u + r22 * in.ob_v) * DT;
-  const double dsx = DT * (q11 * ud + q12 * 0.0), dsy = DT * (q21 * ud + q22 * 0.0);
-  double ox = in.ob_x, oy = in.ob_y;
-  double sx = in.os_x + DT * (q11 * ud + q12 * in.os_v), sy = in.os_y + DT * (q21 * ud + q22 * in.os_v);
-  double t = DT;
-  if constexpr (diag::kNoSbLoop) n_samp = 1;  // (ablation build only: no horizon samples after sample 0)
-  HzBest hb{INFINITY, INFINITY, 0.0, 0.0, false};
-  const HzConst hc{so, co, ovr2, ot2, ah2, cl2, ovr};
-  auto sample = [&](double tt, double d0, double d1, double d2s, bool inr) __attribute__((always_inline)) {
-    hz_sample(hb, hc, tt, d0, d1, d2s, inr);
-  };
-  // two samples per iteration (i, i + 1): their bodies are independent chains the one wave of the SIMD
-  // can interleave; the positions are the same incremental sums as one per iteration, and the samples
-  // enter the running best in order (ties keep the earlier sample).
-  // Split (part 0 / 1): the window of samples that can be in range, [i_first, min(i_last, i_past + 2)], is cut at
-  // its middle; part 1 first advances its positions to the cut by the loop's own sums (a uniform loop, the other
-  // lanes predicated off), then both parts run the loop side by side on their own sample indices.
-  int i_stop = n_samp, i = 1;
-  if (part >= 0) {
-    const int w0 = max(i_first, 1), w1 = max(w0, min(i_last, i_past + 2));
-    const int i_split = min(w0 + (w1 - w0 + 1) / 2, n_samp);
-    if (part == 0) i_stop = i_split;
-    const int i_start = part == 1 ? i_split : 1;
-    for (int c = 1; __any(c < i_start); ++c) {
-      const bool adv = c < i_start, adv_s = adv & (c > 1);
-      ox = adv ? ox + dox : ox;
-      oy = adv ? oy + doy : oy;
-      sx = adv_s ? sx + dsx : sx;
-      sy = adv_s ? sy + dsy : sy;
-      t = adv ? t + DT : t;
-    }
-    i = i_start;
-  }
-  bool done = false;  // past the minimum and beyond the best (see i_past)
-  for (;; i += 2) {
-    // (per lane: a split part has its own sample index; unsplit every lane has the same one)
-    if (!__any((i + 1 < n_samp) & (i <= i_last) & !done & (i < i_stop))) break;  // every lane past its useful samples
-    const double oxa = ox + dox, oya = oy + doy;
-    const double sxa = (i > 1) ? sx + dsx : sx, sya = (i > 1) ? sy + dsy : sy;
-    const double ta = t + DT;
-    ox = oxa + dox;
-    oy = oya + doy;
-    sx = sxa + dsx;
-    sy = sya + dsy;
-    t = ta + DT;
-    const double d0a = oxa - sxa, d1a = oya - sya, d0b = ox - sx, d1b = oy - sy;
-    const double d2a = d0a * d0a + d1a * d1a, d2b = d0b * d0b + d1b * d1b;
-    const bool ia = (d2a < lim2) & (i + 1 < n_samp) & (i < i_stop);
-    const bool ib = (d2b < lim2) & (i + 1 < n_samp) & (i + 1 < i_stop);
-    if (ia | ib) {
-      sample(ta, d0a, d1a, d2a, ia);
-      sample(t, d0b, d1b, d2b, ib);
-    }
-    done = done | ((i + 1 >= i_past) & (hb.s1 < INFINITY) & (t * d2b * d2b > hb.s1 * (1.0 + 2e-10)));
-  }
-  {
-    const bool lo = (i < n_samp) & (i < i_stop);
-    if (__any(lo & (i <= i_last) & !done)) {  // the last sample of an odd count
-      ox = ox + dox;
-      oy = oy + doy;
-      if (i > 1) {
-        sx = sx + dsx;
-        sy = sy + dsy;
-      }
-      t += DT;
-      const double d0 = ox - sx, d1 = oy - sy;
-      const double d2s = d0 * d0 + d1 * d1;
-      if ((d2s < lim2) & lo) sample(t, d0, d1, d2s, true);
-    }
-  }
-  if (part >= 0) {  // the two parts' running bests in sample order: part 0's samples come first
-    // the partner lane (lane ^ 32) by v_permlane32_swap: after the swap of a value with itself the lower half holds
-    // the upper half's value in the second result, the upper half the lower half's in the first
-    const bool upper = part == 1;
-    auto other_u = [&](unsigned x) __attribute__((always_inline)) {
-      const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-      return upper ? r[0] : r[1];
-    };
-    auto other_d = [&](double x) __attribute__((always_inline)) {
-      const unsigned lo = other_u((unsigned)__double2loint(x)), hi = other_u((unsigned)__double2hiint(x));
-      return __hiloint2double((int)hi, (int)lo);
-    };
-    HzBest o;
-    o.s1 = other_d(hb.s1);
-    o.s2 = other_d(hb.s2);
-    o.t1 = other_d(hb.t1);
-    o.q1 = other_d(hb.q1);
-    o.unc = other_u((unsigned)hb.unc) != 0u;
-    const HzBest A = part == 0 ? hb : o, Bp = part == 0 ? o : hb;
-    const bool bwin = Bp.s1 < A.s1;  // (ties keep the earlier sample)
-    hb.s1 = fmin(A.s1, Bp.s1);
-    hb.s2 = fmin(fmin(A.s2, Bp.s2), fmax(A.s1, Bp.s1));  // the second smallest of both
-    hb.t1 = bwin ? Bp.t1 : A.t1;
-    hb.q1 = bwin ? Bp.q1 : A.q1;
-    hb.unc = A.unc | Bp.unc;
-  }
-  const double s1 = hb.s1, s2 = hb.s2, t1 = hb.t1, q1 = hb.q1;
-  if (hb.unc)
-    return sbmpc_scenario_cost_direct(in, n_samp, DT, ud, sp, cp, sp0, cp0, so, co, vo0, vo1, no, max_d_safe, lim2,
-                                      cos_ot, H2);
-  SB_MARK(2);
-  if (s1 < INFINITY) {
-    if (s2 <= s1 * (1.0 + 1e-10))
-      return sbmpc_scenario_cost_direct(in, n_samp, DT, ud, sp, cp, sp0, cp0, so, co, vo0, vo1, no, max_d_safe, lim2,
-                                        cos_ot, H2);
-    const double R = (1 / fabs(t1 - 0.0)) * pow4(d_safe / sqrt(q1));
-    const double k_coll = 1e-6 * os_l * in.obs_l;
-    const double w0 = vs0 - vo0, w1 = vs1 - vo1;
-    const double nrm = sqrt(w0 * w0 + w1 * w1);
-    const double H0 = (k_coll * (nrm * nrm)) * R + 0.0 * 0;
-    if (H0 > H1) H1 = H0;
-  }
-  return H1 + H2;
-}
-
-// Argmin of (cost, index) over each half-wave (its 32 scenario lanes), every lane of the half ending with the
-// result; ties -> the lower index. The order (cost, then index) is a total order on non-NaN costs, so any pairing
-// gives the same result: inside each 16-lane row by DPP (quad xor 1, quad xor 2, row_ror 4, row_ror 8: every lane
-// then holds its row's minimum), then one LDS permute across the half-wave's two rows. Every lane of the wave
-// must be active (the cooperative passes are called wave-uniformly).
-// SHFL: the cross-row step by an LDS permute instead (the multi-obstacle and C1 kernels: the swap's lane-mask select
-// costs them SGPRs they do not have; the same result)
-template <bool SHFL = false>
-__device__ __forceinline__ void scenario_argmin(double& cost, int& idx, int lane) {
-  auto take = [&](double oc, int oi) __attribute__((always_inline)) {
-    if (oc < cost || (oc == cost && oi < idx)) { cost = oc; idx = oi; }
-  };
-  take(dpp_d<kDppQuadXor1>(cost), dpp_i<kDppQuadXor1>(idx));
-  take(dpp_d<kDppQuadXor2>(cost), dpp_i<kDppQuadXor2>(idx));
-  take(dpp_d<kDppRowRor4>(cost), dpp_i<kDppRowRor4>(idx));
-  take(dpp_d<kDppRowRor8>(cost), dpp_i<kDppRowRor8>(idx));
-  // the other row of the half-wave (lane ^ 16) by v_permlane16_swap: after the swap of a value with itself the even
-  // rows hold their partner row's value in the second result, the odd rows in the first
-  if constexpr (SHFL) {
-    take(shfl_d(cost, lane ^ 16), __shfl(idx, lane ^ 16, 64));
-    return;
-  }
-  const bool odd_row = (lane >> 4) & 1;
-  const auto sl = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(cost), (unsigned)__double2loint(cost), false, false);
-  const auto sh = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(cost), (unsigned)__double2hiint(cost), false, false);
-  const auto si = __builtin_amdgcn_permlane16_swap((unsigned)idx, (unsigned)idx, false, false);
-  const double oc = __hiloint2double((int)(odd_row ? sh[0] : sh[1]), (int)(odd_row ? sl[0] : sl[1]));
-  take(oc, (int)(odd_row ? si[0] : si[1]));
-}
-
-// Must be called by every lane of the wave (wave-uniform control flow). `need` marks lanes that
-// request an optimisation with inputs `in`; they receive (P_best, Chi_best). SHIP_UNIFORM: u_d, obs_l and
-// obs_w are the same for every request and set in every lane's `in` (the AST kernels: the ships'
-// configured desired speed and obstacle size), so they are not gathered from the requesting lane.
-template <bool SHIP_UNIFORM = false, bool SHFL_ARGMIN = false>
-__device__ void sbmpc_cooperative(bool need, const SbIn& in, int n_samp, double DT, double& p_best,
-                                  double& chi_best) {
-  SHIPSIM_LANE_CHECK(64, 4);
-  const int lane = opaque_v(threadIdx.x) & 63;  // (opaque: no lane masks held across the caller's loop)
-  const int half = lane >> 5;
-  const int scen = lane & 31;
-  uint64_t req = __ballot(need);
-  while (req) {
-    int src0 = __ffsll((unsigned long long)req) - 1;
-    req &= req - 1;
-    int src1 = -1;
-    if (req) {
-      src1 = __ffsll((unsigned long long)req) - 1;
-      req &= req - 1;
-    }
-    int src = half ? src1 : src0;
-    int srcc = src < 0 ? src0 : src;
-    SbIn g;
-    if constexpr (SHIP_UNIFORM) {
-      g.u_d = in.u_d; g.obs_l = in.obs_l; g.obs_w = in.obs_w;
-    } else {
-      g.u_d = shfl_d(in.u_d, srcc); g.obs_l = shfl_d(in.obs_l, srcc); g.obs_w = shfl_d(in.obs_w, srcc);
-    }
-    g.chi_d = shfl_d(in.chi_d, srcc);
-    g.os_x = shfl_d(in.os_x, srcc); g.os_y = shfl_d(in.os_y, srcc); g.os_v = shfl_d(in.os_v, srcc);
-    g.ob_x = shfl_d(in.ob_x, srcc); g.ob_y = shfl_d(in.ob_y, srcc); g.ob_psi = shfl_d(in.ob_psi, srcc);
-    g.ob_u = shfl_d(in.ob_u, srcc); g.ob_v = shfl_d(in.ob_v, srcc);
-    g.p_last = shfl_d(in.p_last, srcc); g.chi_last = shfl_d(in.chi_last, srcc);
-    g.ob_so = shfl_d(in.ob_so, srcc); g.ob_co = shfl_d(in.ob_co, srcc);
-    double cost = INFINITY;
-    int idx = 64;
-    const bool split = src1 < 0;  // (uniform) one request this pass: both halves take it, each half of every horizon
-    if ((split || src >= 0) && scen < 28) {
-      cost = sbmpc_scenario_cost(g, n_samp, DT, scen >> 2, scen & 3, split ? half : -1);
-      idx = scen;
-    }
-    // argmin over the half-wave; ties -> lowest scenario index (first strict improvement in the
-    // reference's i-major / j-minor loop)
-    scenario_argmin<SHFL_ARGMIN>(cost, idx, lane);
-    const int best0 = __builtin_amdgcn_readlane(idx, 0);
-    const int best1 = __builtin_amdgcn_readlane(idx, 32);
-    if (lane == src0) {
-      p_best = p_ca_of(best0 & 3);
-      chi_best = (-30.0 + 10.0 * (best0 >> 2)) * (kPi / 180.0);
-    }
-    if (src1 >= 0 && lane == src1) {
-      p_best = p_ca_of(best1 & 3);
-      chi_best = (-30.0 + 10.0 * (best1 >> 2)) * (kPi / 180.0);
-    }
-  }
-}
-
-// SBMPC over a do_list of NOB obstacles (sbmpc.py:150-183; env.py:366-370 passes every obstacle ship):
-// per scenario the worst obstacle's cost (cost_i = -1, then every strictly larger cost_k: the max of the costs),
-// the scenario with the least worst cost wins (lowest index on ties). Slots of an env that duplicate its last
-// ship repeat an obstacle, which changes neither the max nor the D_INIT test, and are not evaluated.
-// Lanes: scenario = lane & 31 (28 used). With two or more requests pending a pass serves two, one per half-wave,
-// each lane taking its scenario's obstacles in turn; with one request both halves serve it and split its
-// obstacles — half h takes obstacles h, h + 2, … — and the two halves' worst costs are merged (lane ^ 32) before
-// the argmin, so a lone request costs ⌈K / 2⌉ scenario evaluations per lane instead of K (the max over the same
-// set of costs: the same value in either order).
-template <int NOB>
-struct SbMulti {
-  double u_d, chi_d, os_x, os_y, os_v, p_last, chi_last;
-  double ob_x[NOB], ob_y[NOB], ob_psi[NOB], ob_u[NOB], ob_v[NOB], obs_l[NOB], obs_w[NOB];
-};
-
-template <int NOB>
-__device__ __forceinline__ void sbmpc_cooperative_multi(bool need, const SbMulti<NOB>& in, int n_obs, int n_samp, double DT,
-                                        double& p_best, double& chi_best) {
-  SHIPSIM_LANE_CHECK(64, 4);
-  const int lane = opaque_v(threadIdx.x) & 63;
-  const int half = lane >> 5;
-  const int scen = lane & 31;
-  uint64_t req = __ballot(need);
-  diag::sb_stat_wave(0, req ? 1u : 0u);
-  while (req) {
-    // the counts re-derived per pass: tests on them are not hoisted out of this loop and held across it
-    const int n_obs_p = opaque_s(n_obs), n_samp_p = opaque_s(n_samp);
-    int src0 = __ffsll((unsigned long long)req) - 1;
-    req &= req - 1;
-    int src1 = -1;
-    if (req) {
-      src1 = __ffsll((unsigned long long)req) - 1;
-      req &= req - 1;
-    }
-    const bool split = src1 < 0;  // (uniform) one request this pass: the halves split its obstacles
-    diag::sb_stat_wave(1, 1u);
-    diag::sb_stat_wave(2, split ? 1u : 0u);
-    diag::sb_stat_wave(3, split ? 1u : 2u);
-    int src = half ? src1 : src0;
-    const int srcc = src < 0 ? src0 : src;
-    SbIn g;
-    g.u_d = shfl_d(in.u_d, srcc); g.chi_d = shfl_d(in.chi_d, srcc);
-    g.os_x = shfl_d(in.os_x, srcc); g.os_y = shfl_d(in.os_y, srcc); g.os_v = shfl_d(in.os_v, srcc);
-    g.p_last = shfl_d(in.p_last, srcc); g.chi_last = shfl_d(in.chi_last, srcc);
-    double cost = INFINITY;
-    int idx = 64;
-    double worst = -1.0;
-    bool any_far = false;
-    const bool act = (split || src >= 0) && scen < 28;
-    // obstacles in pairs (2j, 2j + 1): split, half h takes obstacle 2j + h; otherwise each lane both, in order
-#pragma unroll
-    for (int j = 0; j < (NOB + 1) / 2; ++j) {
-      const int ka = 2 * j, kb = 2 * j + 1 < NOB ? 2 * j + 1 : 2 * j;
-      if (ka >= n_obs_p) break;  // (wave-uniform) slots past the env's K obstacles duplicate the last one
-      const bool b_ok = 2 * j + 1 < NOB && 2 * j + 1 < n_obs_p;
-      for (int t = 0; t < (split ? 1 : 2); ++t) {  // (uniform trip count)
-        const bool use_b = split ? half == 1 : t == 1;
-        // this lane's obstacle, field by field (both candidates gathered, one kept: short live ranges)
-        auto pick = [&](const double (&f)[NOB]) __attribute__((always_inline)) {
-          const double a = shfl_d(f[ka], srcc);
-          const double b = shfl_d(f[kb], srcc);
-          return use_b ? b : a;
-        };
-        SbIn q = g;
-        q.ob_x = pick(in.ob_x); q.ob_y = pick(in.ob_y); q.ob_psi = pick(in.ob_psi);
-        q.ob_u = pick(in.ob_u); q.ob_v = pick(in.ob_v); q.obs_l = pick(in.obs_l); q.obs_w = pick(in.obs_w);
-        const bool ok = act && (use_b ? b_ok : true);
-        // an obstacle out of reach costs exactly sbmpc_h2 in every scenario (added once below)
-        const bool far = ok && sbmpc_far(q, n_samp_p, DT);
-        any_far = any_far || far;
-        diag::sb_stat_lanes(4, (ok && !far) ? 1u : 0u);
-        diag::sb_stat_lanes(5, far ? 1u : 0u);
-        if (ok && !far) {
-          sb_set_heading_trig(q);
-          const double ck = sbmpc_scenario_cost(q, opaque_s(n_samp_p), DT, scen >> 2, scen & 3);
-          if (ck > worst) worst = ck;
-        }
-      }
-    }
-    if (act && any_far) {
-      const double h2 = sbmpc_h2(g, scen >> 2, scen & 3);
-      if (h2 > worst) worst = h2;
-    }
-    if (split) {  // (uniform) the other half's worst over its obstacles (lane ^ 32)
-      const double ow = shfl_d(worst, lane ^ 32);
-      if (ow > worst) worst = ow;
-    }
-    if (act) {
-      cost = worst;
-      idx = scen;
-    }
-    scenario_argmin<true>(cost, idx, lane);
-    const int best0 = __builtin_amdgcn_readlane(idx, 0);
-    const int best1 = __builtin_amdgcn_readlane(idx, 32);
-    if (lane == src0) {
-      p_best = p_ca_of(best0 & 3);
-      chi_best = (-30.0 + 10.0 * (best0 >> 2)) * (kPi / 180.0);
-    }
-    if (src1 >= 0 && lane == src1) {
-      p_best = p_ca_of(best1 & 3);
-      chi_best = (-30.0 + 10.0 * (best1 >> 2)) * (kPi / 180.0);
-    }
-  }
-}
+#include "shipsim_sbmpc.hpp"  // the wave-cooperative SBMPC optimiser
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -2479,135 +1736,6 @@ __global__ __launch_bounds__(64) void single_tick_kernel(const Params P, DevStat
   store_ship(S, q, s);
 }
 
-#endif  // SHIPSIM_TU != 2
-
-#if SHIPSIM_TU != 1
-// C2 with the simplified machinery (the C2 configuration, SimpleShipModel + ThrustFromSpeedSetPoint): the same ticks
-// as single_tick_kernel<false>, bit for bit, on THREE waves per 64 ships, software-pipelined so that one workgroup
-// barrier per tick separates them. A tick t only needs, besides its own (u, v, r):
-//   sin/cos ψ_t    — ψ_t = ψ_{t-1} + r_{t-1} dt is known one tick early;
-//   the rudder_t   — waypoint switch, LOS guidance (sqrt, divide, atan) and heading PID on (n, e, ψ)_t, which follow
-//                    from tick t - 1's state by the explicit Euler step before tick t - 1's kinetics matter.
-// So in interval t
-//   wave 0 (guidance): (n, e, ψ)_{t+1} from (u, v, r)_t and sin/cos ψ_t, then the rudder of tick t + 1;
-//   wave 1 (heading):  ψ_{t+1} and sin/cos ψ_{t+1};
-//   wave 2 (dynamics): tick t's thrust (speed PID), wind force and kinetics -> (u, v, r)_{t+1};
-// each reading what the others wrote in interval t - 1 (LDS, double-buffered by tick parity). Every value is formed
-// by the same expression as in the one-wave tick (control_and_store, differentials, integrate): the same bits.
-template <bool POW2_DT>  // dt a power of two: the PIDs' derivative division as the exact multiplication (pid)
-__global__ __launch_bounds__(192) void single_tick_pipe_kernel(const Params P, DevState S, ConstBuf K, int k) {
-  __shared__ ShipConst lds_sc[SHIPSIM_MAX_SHIPS];
-  __shared__ double x_uvr[2][3][64];  // (u, v, r) of a tick, by tick parity
-  __shared__ double x_sc[2][2][64];   // sin / cos ψ of a tick
-  __shared__ double x_rud[2][64];     // rudder of a tick
-  const ShipConst* SC = stage_consts(K, lds_sc, P.n_ships, P.dt);
-  const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;  // (wave-uniform)
-  const int q0 = blockIdx.x * 64 + lane, q = min(q0, P.n_envs - 1);  // (every lane takes part in the barriers)
-  const bool live = q0 < P.n_envs;
-  const ShipConst& c = SC[0];
-  const double dt = P.dt, inv_dt = pow2_inverse(dt);  // (the PIDs' derivative terms: see pid)
-  Ship s;
-  load_ship(S, q, s);
-  // the kinematic rates of integrate's Euler step (differentials_body's expressions)
-  auto advance_pose = [&](double u, double v, double r, double sy, double cy) __attribute__((always_inline)) {
-    // (the rotation's structural zero terms dropped: a ±0 addend leaves every non-zero rate's bits as they are)
-    const double dn = cy * u + (-sy) * v;
-    const double de = sy * u + cy * v;
-    const double dyaw = r;
-    s.n = s.n + dn * dt;
-    s.e = s.e + de * dt;
-    s.yaw = s.yaw + dyaw * dt;
-  };
-  if (role == 0) {
-    // guidance: the rudder of tick j from (n, e, ψ)_j — control_and_store's route half (DETAILED false, no collav)
-    const double* rn = S.route_n() + (size_t)q * kMaxRoute;
-    const double* re = S.route_e() + (size_t)q * kMaxRoute;
-    auto guide = [&]() __attribute__((always_inline)) {
-      const double N = s.n, E = s.e, H = s.yaw;
-      if (next_wpt_advance(c, s, N, E)) {
-        s.next_wpt += 1;
-        load_segment(s, rn, re);
-      }
-      const double href = los_guidance(c, s, N, E);
-      const double rudder = heading_ctrl<POW2_DT>(c, s, href + 0.0, H, dt, POW2_DT ? inv_dt : c.rcp_dt);
-      s.log_rudder = rudder;
-      s.log_ect = s.e_ct;
-      s.log_n = N;
-      s.log_e = E;
-      return rudder;
-    };
-    x_rud[0][lane] = guide();
-    __syncthreads();
-    for (int t = 0; t < k; ++t) {
-      const int b = t & 1;
-      advance_pose(x_uvr[b][0][lane], x_uvr[b][1][lane], x_uvr[b][2][lane], x_sc[b][0][lane], x_sc[b][1][lane]);
-      if (t + 1 < k) x_rud[b ^ 1][lane] = guide();
-      __syncthreads();
-    }
-    if (live) {
-      S.f(SF_N)[q] = s.n; S.f(SF_E)[q] = s.e; S.f(SF_YAW)[q] = s.yaw;
-      S.f(SF_ECT)[q] = s.e_ct; S.f(SF_ECT_INT)[q] = s.e_ct_int;
-      S.f(SF_HDG_EI)[q] = s.hdg_ei; S.f(SF_HDG_PREV)[q] = s.hdg_prev;
-      S.f(SF_RUDDER)[q] = s.log_rudder; S.f(SF_LOG_ECT)[q] = s.log_ect;
-      S.f(SF_LOG_N)[q] = s.log_n; S.f(SF_LOG_E)[q] = s.log_e;
-      S.next_wpt()[q] = s.next_wpt;
-    }
-  } else if (role == 1) {
-    // heading: sin/cos ψ of the next tick (differentials' sincos(s.yaw))
-    double sy, cy;
-    sincos(s.yaw, &sy, &cy);
-    x_sc[0][0][lane] = sy; x_sc[0][1][lane] = cy;
-    __syncthreads();
-    for (int t = 0; t < k; ++t) {
-      const int b = t & 1;
-      const double r = x_uvr[b][2][lane];
-      s.yaw = s.yaw + r * dt;  // (advance_pose's ψ rate)
-      if (t + 1 < k) {
-        sincos(s.yaw, &sy, &cy);
-        x_sc[b ^ 1][0][lane] = sy; x_sc[b ^ 1][1][lane] = cy;
-      }
-      __syncthreads();
-    }
-  } else {
-    // dynamics: tick t's thrust, wind force and kinetics (control_and_store's speed half, differentials, integrate)
-    double wsin, wcos;
-    sincos(P.wind_dir, &wsin, &wcos);
-    x_uvr[0][0][lane] = s.u; x_uvr[0][1][lane] = s.v; x_uvr[0][2][lane] = s.r;
-    __syncthreads();
-    for (int t = 0; t < k; ++t) {
-      const int b = t & 1;
-      const double sy = x_sc[b][0][lane], cy = x_sc[b][1][lane], rudder = x_rud[b][lane];
-      const double thrust = speed_ctrl<POW2_DT>(c, s, c.desired_speed * 1.0, s.u, dt, false, POW2_DT ? inv_dt : c.rcp_dt);
-      s.log_thrust = thrust;
-      double tau[3];
-      wind_force_alg(c, P, s, sy, cy, wsin, wcos, tau);
-      const Deriv d = differentials_body(c, P, s, thrust, rudder, false, sy, cy, tau);
-      s.u = s.u + d.du * dt;
-      s.v = s.v + d.dv * dt;
-      s.r = s.r + d.dr * dt;
-      s.time = s.time + dt;
-      x_uvr[b ^ 1][0][lane] = s.u; x_uvr[b ^ 1][1][lane] = s.v; x_uvr[b ^ 1][2][lane] = s.r;
-      __syncthreads();
-    }
-    if (live) {
-      S.f(SF_U)[q] = s.u; S.f(SF_V)[q] = s.v; S.f(SF_R)[q] = s.r; S.f(SF_TIME)[q] = s.time;
-      S.f(SF_SPD_A)[q] = s.spd_a; S.f(SF_SPD_B)[q] = s.spd_b; S.f(SF_THRUST)[q] = s.log_thrust;
-    }
-  }
-}
-
-#endif  // SHIPSIM_TU != 1
-
-#if SHIPSIM_TU != 1
-void shipsim_c2_pipe_launch(int blocks, hipStream_t st, const Params& P, const DevState& S, const ConstBuf& K, int k) {
-  if (pow2_inverse(P.dt) != 0.0)
-    hipLaunchKernelGGL(single_tick_pipe_kernel<true>, dim3(blocks), dim3(192), 0, st, P, S, K, k);
-  else
-    hipLaunchKernelGGL(single_tick_pipe_kernel<false>, dim3(blocks), dim3(192), 0, st, P, S, K, k);
-}
-#endif
-
-#if SHIPSIM_TU != 2
 // Legacy per-tick MultiShipEnv.step (rl_env/ship_in_transit/env.py:1104-1173), k steps per launch.
 // Two lanes per env (lane & 1 = ship); the termination flags of get_termination_status
 // (termination_flags.py:5-70) are evaluated in fp64 on the next_states, as the reference does on
@@ -3064,75 +2192,6 @@ struct shipsim_handle {
   char err[512];
 };
 
-// ---------------------------------------------------------------------------------------------
-// map grid (host): exact, conservative cell classification used by corner_inside / map_dist2_mask
-// ---------------------------------------------------------------------------------------------
-static const double kGridCell = 200.0;     // m
-static const double kGridPad = 2000.0;     // m of grid beyond the polygon bounding box
-static const double kGridEps = 1e-3;       // m: cells are enlarged by this before classification
-
-// segment vs closed axis-aligned rectangle (Liang-Barsky clip)
-static bool seg_hits_rect(const Edge& ed, double x0, double y0, double x1, double y1) {
-  double t0 = 0.0, t1 = 1.0;
-  const double dx = ed.bx - ed.ax, dy = ed.by - ed.ay;
-  const double p[4] = {-dx, dx, -dy, dy};
-  const double q[4] = {ed.ax - x0, x1 - ed.ax, ed.ay - y0, y1 - ed.ay};
-  for (int i = 0; i < 4; ++i) {
-    if (p[i] == 0.0) {
-      if (q[i] < 0.0) return false;
-    } else {
-      const double t = q[i] / p[i];
-      if (p[i] < 0.0) { if (t > t1) return false; if (t > t0) t0 = t; }
-      else { if (t < t0) return false; if (t < t1) t1 = t; }
-    }
-  }
-  return true;
-}
-static double point_seg_dist(double px, double py, const Edge& ed) {
-  const double dx = ed.bx - ed.ax, dy = ed.by - ed.ay, l2 = dx * dx + dy * dy;
-  double t = l2 > 0 ? ((px - ed.ax) * dx + (py - ed.ay) * dy) / l2 : 0.0;
-  t = t < 0 ? 0 : (t > 1 ? 1 : t);
-  const double ex = ed.ax + t * dx - px, ey = ed.ay + t * dy - py;
-  return sqrt(ex * ex + ey * ey);
-}
-static double point_rect_dist(double px, double py, double x0, double y0, double x1, double y1) {
-  const double dx = px < x0 ? x0 - px : (px > x1 ? px - x1 : 0.0);
-  const double dy = py < y0 ? y0 - py : (py > y1 ? py - y1 : 0.0);
-  return sqrt(dx * dx + dy * dy);
-}
-static double seg_rect_dist(const Edge& ed, double x0, double y0, double x1, double y1) {
-  if (seg_hits_rect(ed, x0, y0, x1, y1)) return 0.0;
-  double d = point_rect_dist(ed.ax, ed.ay, x0, y0, x1, y1);
-  d = py_min(d, point_rect_dist(ed.bx, ed.by, x0, y0, x1, y1));
-  d = py_min(d, point_seg_dist(x0, y0, ed));
-  d = py_min(d, point_seg_dist(x1, y0, ed));
-  d = py_min(d, point_seg_dist(x0, y1, ed));
-  d = py_min(d, point_seg_dist(x1, y1, ed));
-  return d;
-}
-// Fills mask/flag for a gnx x gny grid. A cell no edge touches is uniformly inside or outside
-// (the polygons' boundary is the union of their edges), so its center decides it; any cell an
-// edge touches is MIXED and gets the full test. Edge masks keep every edge within kGroundReach of
-// the enlarged cell (+1 mm slack on the reach for rounding).
-static void build_grid(const Edge* E, int n_edges, const PolyBox* B, int n_polys, double gx0, double gy0, int gnx,
-                       int gny, uint64_t* mask, uint8_t* flag) {
-  for (int j = 0; j < gny; ++j)
-    for (int i = 0; i < gnx; ++i) {
-      const double x0 = gx0 + i * kGridCell - kGridEps, x1 = gx0 + (i + 1) * kGridCell + kGridEps;
-      const double y0 = gy0 + j * kGridCell - kGridEps, y1 = gy0 + (j + 1) * kGridCell + kGridEps;
-      uint64_t m = 0;
-      bool touched = false;
-      for (int k = 0; k < n_edges; ++k) {
-        const double d = seg_rect_dist(E[k], x0, y0, x1, y1);
-        if (d <= kGroundReach + kGridEps) m |= (uint64_t)1 << k;
-        if (d == 0.0) touched = true;
-      }
-      mask[(size_t)j * gnx + i] = m;
-      const double cx = 0.5 * (x0 + x1), cy = 0.5 * (y0 + y1);
-      flag[(size_t)j * gnx + i] = touched ? GRID_MIXED : (map_inside(E, B, n_polys, cy, cx) ? GRID_IN : GRID_OUT);
-    }
-}
-
 static int fail(shipsim_handle* h, int code, const char* fmt, ...) {
   if (h) {
     va_list ap;
@@ -3283,264 +2342,8 @@ const char* shipsim_build_info(void) {
   return "shipsim gfx950 HIP (fp64, lane-pair AST kernel, wave-cooperative SBMPC) src " SHIPSIM_SRC_HASH;
 }
 
-static void fill_ship_common(shipsim_ship_config* s, double n, double e, double yaw, double u) {
-  memset(s, 0, sizeof(*s));
-  s->coefficient_of_deadweight_to_displacement = 0.7;
-  s->bunkers = 200000;
-  s->ballast = 200000;
-  s->length_of_ship = 80;
-  s->width_of_ship = 16;
-  s->added_mass_coefficient_in_surge = 0.4;
-  s->added_mass_coefficient_in_sway = 0.4;
-  s->added_mass_coefficient_in_yaw = 0.4;
-  s->dead_weight_tonnage = 3850000;
-  s->mass_over_linear_friction_coefficient_in_surge = 130;
-  s->mass_over_linear_friction_coefficient_in_sway = 18;
-  s->mass_over_linear_friction_coefficient_in_yaw = 90;
-  s->nonlinear_friction_coefficient_in_surge = 2400;
-  s->nonlinear_friction_coefficient_in_sway = 4000;
-  s->nonlinear_friction_coefficient_in_yaw = 400;
-  s->initial_north_position_m = n;
-  s->initial_east_position_m = e;
-  s->initial_yaw_angle_rad = yaw;
-  s->initial_forward_speed_m_per_s = u;
-  s->rudder_angle_to_sway_force_coefficient = 50e3;
-  s->rudder_angle_to_yaw_force_coefficient = 500e3;
-  s->max_rudder_angle_degrees = 30;
-  s->hotel_load = 200000;
-  s->main_engine_capacity = 0;
-  s->electrical_capacity = 2 * 510e3;
-  s->shaft_generator_state = SHIPSIM_SG_MOTOR;
-  s->rated_speed_main_engine_rpm = 1000;
-  s->linear_friction_main_engine = 68;
-  s->linear_friction_hybrid_shaft_generator = 57;
-  s->gear_ratio_between_main_engine_and_propeller = 0.6;
-  s->gear_ratio_between_hybrid_shaft_generator_and_propeller = 0.6;
-  s->propeller_inertia = 6000;
-  s->propeller_diameter = 3.1;
-  s->propeller_speed_to_torque_coefficient = 7.5;
-  s->propeller_speed_to_thrust_force_coefficient = 1.7;
-  s->kp_ship_speed = 205.25;
-  s->ki_ship_speed = 0.0525;
-  s->kp_shaft_speed = 50;
-  s->ki_shaft_speed = 0.00025;
-  s->initial_shaft_speed_integral_error = 114;
-  s->max_thrust = INFINITY;
-  s->radius_of_acceptance = 300;
-  s->lookahead_distance = 1000;
-  s->los_integral_gain = 0.002;
-  s->los_integrator_windup_limit = 4000;
-}
-
-static void set_route(shipsim_ship_config* s, const double (*r)[2], int n) {
-  s->n_route = n;
-  for (int i = 0; i < n; ++i) {
-    s->route_north[i] = r[i][0];
-    s->route_east[i] = r[i][1];
-  }
-}
-
 int shipsim_default_config(int32_t kind, int32_t machinery, int32_t collav, double time_step, shipsim_config* cfg) {
-  if (!cfg || kind < 0 || kind > 2 || machinery < 0 || machinery > 1 || collav < 0 || collav > 2) return SHIPSIM_EINVAL;
-  static const double map_e_n[][2] = {
-      {0, 10000}, {10000, 10000}, {9200, 9000}, {7600, 8500}, {6700, 7300}, {4900, 6500}, {4300, 5400},
-      {4700, 4500}, {6000, 4000}, {5800, 3600}, {4200, 3200}, {3200, 4100}, {2000, 4500}, {1000, 4000},
-      {900, 3500}, {500, 2600}, {0, 2350},
-      {10000, 0}, {11500, 750}, {12000, 2000}, {11700, 3000}, {11000, 3600}, {11250, 4250}, {12300, 4000},
-      {13000, 3800}, {14000, 3000}, {14500, 2300}, {15000, 1700}, {16000, 800}, {17500, 0},
-      {15500, 10000}, {16000, 9000}, {18000, 8000}, {19000, 7500}, {20000, 6000}, {20000, 10000},
-      {5500, 5300}, {6000, 5000}, {6800, 4500}, {8000, 5000}, {8700, 5500}, {9200, 6700}, {8000, 7000},
-      {6700, 6300}, {6000, 6000},
-      {15000, 5000}, {14000, 5500}, {12500, 5000}, {14000, 4100}, {16000, 2000}, {15700, 3700},
-      {11000, 2000}, {10300, 3200}, {9000, 1500}, {10000, 1000}};
-  static const int poly_counts[6] = {17, 13, 6, 9, 6, 4};
-  static const double test_route[7][2] = {{0, 0}, {2000, 4500}, {2500, 7500}, {7000, 12000}, {6500, 16000},
-                                          {3000, 17500}, {0, 20000}};
-  static const double obs_route[2][2] = {{10000, 15000}, {0, 5000}};
-  static const double obs_route_noniw[11][2] = {{10000, 15000}, {9500, 13500}, {8000, 13000}, {6500, 12500},
-                                                {6000, 11000}, {5500, 9500}, {4000, 9000}, {2500, 8500},
-                                                {2000, 7000}, {1500, 5500}, {0, 5000}};
-  memset(cfg, 0, sizeof(*cfg));
-  cfg->abi_version = SHIPSIM_ABI_VERSION;
-  cfg->kind = kind;
-  cfg->machinery = machinery;
-  cfg->collav = collav;
-  cfg->max_sampling_frequency = 9;
-  cfg->machinery_dt_quirk = 1;
-  cfg->normalize_action = 0;
-  cfg->n_ships = kind == SHIPSIM_KIND_SINGLE ? 1 : 2;
-  cfg->time_step = time_step;
-  cfg->simulation_time = 10000;
-  cfg->env_radius_of_acceptance = 300;
-  cfg->current_velocity_component_from_north = -1;
-  cfg->current_velocity_component_from_east = -1;
-  cfg->wind_speed = 2;
-  cfg->wind_direction = -M_PI / 4;
-  cfg->sbmpc_tf = 1000;
-  cfg->sbmpc_dt = 20;
-  shipsim_ship_config* t = &cfg->ship[0];
-  shipsim_ship_config* o = &cfg->ship[1];
-  fill_ship_common(t, 100, 100, 60 * M_PI / 180, 4.25);
-  fill_ship_common(o, 9900, 14900, -135 * M_PI / 180, 3.5);
-  set_route(t, test_route, 7);
-  t->desired_forward_speed = 4.5;
-  o->desired_forward_speed = 4.0;
-  if (kind == SHIPSIM_KIND_AST) {  // run/env_setup.py
-    t->initial_propeller_shaft_speed_rad_per_s = 420 * M_PI / 30;
-    o->initial_propeller_shaft_speed_rad_per_s = 200 * M_PI / 30;
-    for (int i = 0; i < 2; ++i) {
-      cfg->ship[i].heading_kp = 1.65; cfg->ship[i].heading_kd = 75; cfg->ship[i].heading_ki = 0.001;
-      cfg->ship[i].speed_kp = 150; cfg->ship[i].speed_ki = 150; cfg->ship[i].speed_kd = 75;
-    }
-    set_route(o, obs_route, 2);
-    cfg->action_low = (float)(-(30 * (M_PI / 180.0)));
-    cfg->action_high = (float)(30 * (M_PI / 180.0));
-  } else {  // run_colav/run_simplified_model.py
-    t->speed_kp = 150; t->speed_ki = 150; t->speed_kd = 75;
-    o->speed_kp = .025; o->speed_ki = 700.5; o->speed_kd = 550.5;
-    t->heading_kp = .5; t->heading_ki = 0.01; t->heading_kd = 84;
-    o->heading_kp = .65; o->heading_ki = 0.001; o->heading_kd = 50;
-    set_route(o, obs_route_noniw, 11);
-    cfg->action_low = (float)(-M_PI / 6);
-    cfg->action_high = (float)(M_PI / 6);
-  }
-  int k = 0, p = 0;
-  for (p = 0; p < 6; ++p) {
-    cfg->poly_start[p] = k;
-    for (int i = 0; i < poly_counts[p]; ++i, ++k) {
-      cfg->poly_east[k] = map_e_n[k][0];
-      cfg->poly_north[k] = map_e_n[k][1];
-    }
-  }
-  cfg->poly_start[6] = k;
-  cfg->n_polys = 6;
-  return SHIPSIM_OK;
-}
-
-// host restatement of the constructors' derived constants (ship_model.py:412-474,
-// ship_engine.py:32-44, 341-401)
-static void make_ship_const(const shipsim_config* cfg, const shipsim_ship_config* c, ShipConst* k) {
-  memset(k, 0, sizeof(*k));
-  double payload = 0.9 * (c->dead_weight_tonnage - c->bunkers);
-  double lsw = c->dead_weight_tonnage / c->coefficient_of_deadweight_to_displacement - c->dead_weight_tonnage;
-  k->mass = lsw + payload + c->bunkers + c->ballast;
-  k->l_ship = c->length_of_ship;
-  k->w_ship = c->width_of_ship;
-  k->obs_l_cfg = c->length_of_ship;
-  k->obs_w_cfg = c->width_of_ship;
-  k->i_z = k->mass * (k->l_ship * k->l_ship + k->w_ship * k->w_ship) / 12;
-  k->x_du = k->mass * c->added_mass_coefficient_in_surge;
-  k->y_dv = k->mass * c->added_mass_coefficient_in_sway;
-  k->n_dr = k->i_z * c->added_mass_coefficient_in_yaw;
-  k->inv_m0 = 1.0 / (k->mass + k->x_du);
-  k->inv_m1 = 1.0 / (k->mass + k->y_dv);
-  k->inv_m2 = 1.0 / (k->i_z + k->n_dr);
-  k->dlin0 = k->mass / c->mass_over_linear_friction_coefficient_in_surge;
-  k->dlin1 = k->mass / c->mass_over_linear_friction_coefficient_in_sway;
-  k->dlin2 = k->i_z / c->mass_over_linear_friction_coefficient_in_yaw;
-  k->ku = c->nonlinear_friction_coefficient_in_surge;
-  k->kv = c->nonlinear_friction_coefficient_in_sway;
-  k->kr = c->nonlinear_friction_coefficient_in_yaw;
-  k->rho_a = 1.2;
-  k->proj_area_f = k->w_ship * 8.0;
-  k->proj_area_l = k->l_ship * 8.0;
-  k->cx = 0.5;
-  k->cy = 0.7;
-  k->cn = 0.08;
-  k->c_rudder_v = c->rudder_angle_to_sway_force_coefficient;
-  k->c_rudder_r = c->rudder_angle_to_yaw_force_coefficient;
-  k->max_rudder = c->max_rudder_angle_degrees * M_PI / 180;
-  double me = c->main_engine_capacity, el = c->electrical_capacity, hl = c->hotel_load;
-  if (c->shaft_generator_state == SHIPSIM_SG_MOTOR) {
-    k->avail_me = me;
-    k->avail_el = el - hl;
-  } else if (c->shaft_generator_state == SHIPSIM_SG_GEN) {
-    k->avail_me = me - hl;
-    k->avail_el = 0;
-  } else {
-    k->avail_me = me;
-    k->avail_el = 0;
-  }
-  k->cap_me = k->avail_me / 5 * M_PI / 30;
-  k->cap_el = k->avail_el / 5 * M_PI / 30;
-  k->d_me = c->linear_friction_main_engine;
-  k->d_hsg = c->linear_friction_hybrid_shaft_generator;
-  k->r_me = c->gear_ratio_between_main_engine_and_propeller;
-  k->r_hsg = c->gear_ratio_between_hybrid_shaft_generator_and_propeller;
-  k->jp = c->propeller_inertia;
-  k->kp_prop = c->propeller_speed_to_torque_coefficient;
-  k->thrust_coeff = pow(c->propeller_diameter, 4) * c->propeller_speed_to_thrust_force_coefficient;
-  k->shaft_speed_max = 1.1 * (c->rated_speed_main_engine_rpm * M_PI / 30) * k->r_me;
-  k->init_omega = c->initial_propeller_shaft_speed_rad_per_s;
-  k->mode_me = me;
-  k->mode_el = el;
-  k->hotel = hl;
-  k->avail_prop = (c->shaft_generator_state == SHIPSIM_SG_MOTOR) ? me + el - hl
-                  : (c->shaft_generator_state == SHIPSIM_SG_GEN) ? me - hl : me;  // :32-44
-  k->sg_state = c->shaft_generator_state;
-  // run/env_setup.py:85-104: SpecificFuelConsumptionWartila6L26 (ME) / Baudouin6M26Dot3 (DG),
-  // ship_engine.py:88-112 (BaseMachineryModel.fuel_consumption uses these, not the
-  // ShipMachineryModel.specific_fuel_coeffs_* literals)
-  k->fa_me = 128.9; k->fb_me = -168.9; k->fc_me = 246.8;
-  k->fa_dg = 108.7; k->fb_dg = -289.9; k->fc_dg = 324.9;
-  k->kp_ship_speed = c->kp_ship_speed;
-  k->ki_ship_speed = c->ki_ship_speed;
-  k->kp_shaft_speed = c->kp_shaft_speed;
-  k->ki_shaft_speed = c->ki_shaft_speed;
-  k->init_shaft_ei = c->initial_shaft_speed_integral_error;
-  k->spd_kp = c->speed_kp;
-  k->spd_ki = c->speed_ki;
-  k->spd_kd = c->speed_kd;
-  k->max_thrust = c->max_thrust;
-  k->hdg_kp = c->heading_kp;
-  k->hdg_kd = c->heading_kd;
-  k->hdg_ki = c->heading_ki;
-  k->ra2 = c->radius_of_acceptance * c->radius_of_acceptance;
-  k->los_r = c->lookahead_distance;
-  k->los_r2 = c->lookahead_distance * c->lookahead_distance;
-  k->los_ki = c->los_integral_gain;
-  k->los_limit = c->los_integrator_windup_limit;
-  k->desired_speed = c->desired_forward_speed;
-  k->init_n = c->initial_north_position_m;
-  k->init_e = c->initial_east_position_m;
-  k->init_yaw = c->initial_yaw_angle_rad;
-  k->init_u = c->initial_forward_speed_m_per_s;
-  k->init_v = c->initial_sideways_speed_m_per_s;
-  k->init_r = c->initial_yaw_rate_rad_per_s;
-  k->n_route = c->n_route;
-  (void)cfg;
-}
-
-static int validate(const shipsim_config* cfg, char* err, size_t n) {
-  if (cfg->abi_version != SHIPSIM_ABI_VERSION) return snprintf(err, n, "abi_version %d != %d", cfg->abi_version, SHIPSIM_ABI_VERSION), 1;
-  if (cfg->kind < 0 || cfg->kind > 2) return snprintf(err, n, "bad kind %d", cfg->kind), 1;
-  if (cfg->machinery < 0 || cfg->machinery > 1) return snprintf(err, n, "bad machinery %d", cfg->machinery), 1;
-  if (cfg->collav < 0 || cfg->collav > 2) return snprintf(err, n, "bad collav %d", cfg->collav), 1;
-  int ns = cfg->kind == SHIPSIM_KIND_SINGLE ? 1 : 2;
-  if (cfg->kind == SHIPSIM_KIND_AST) {
-    ns = cfg->n_ships;
-    if (ns < 2 || ns > SHIPSIM_MAX_SHIPS)
-      return snprintf(err, n, "n_ships %d: 1 ship under test + 1..%d obstacle ships", ns, SHIPSIM_MAX_OBS), 1;
-    const char* why = launch_host::select(cfg->machinery, cfg->collav, ns, 16, false, false, launch_host::kStep).why;
-    if (why) return snprintf(err, n, "%d obstacle ships: %s", ns - 1, why), 1;
-  }
-  if (cfg->n_ships != ns) return snprintf(err, n, "n_ships %d != %d for kind %d", cfg->n_ships, ns, cfg->kind), 1;
-  if (!(cfg->time_step > 0)) return snprintf(err, n, "time_step must be > 0"), 1;
-  if (cfg->max_sampling_frequency < 0 || cfg->max_sampling_frequency + 2 > SHIPSIM_MAX_ROUTE)
-    return snprintf(err, n, "max_sampling_frequency %d out of range", cfg->max_sampling_frequency), 1;
-  for (int i = 0; i < ns; ++i) {
-    int nr = cfg->ship[i].n_route;
-    if (nr < 2 || nr > SHIPSIM_MAX_ROUTE) return snprintf(err, n, "ship %d route length %d out of range", i, nr), 1;
-    if (cfg->kind == SHIPSIM_KIND_AST && i == 1 && nr + cfg->max_sampling_frequency > SHIPSIM_MAX_ROUTE)
-      return snprintf(err, n, "obstacle route %d + samplings %d exceeds %d", nr, cfg->max_sampling_frequency, SHIPSIM_MAX_ROUTE), 1;
-  }
-  if (cfg->n_polys < 0 || cfg->n_polys > SHIPSIM_MAX_POLYS) return snprintf(err, n, "n_polys %d out of range", cfg->n_polys), 1;
-  if (cfg->poly_start[0] != 0 || cfg->poly_start[cfg->n_polys] > SHIPSIM_MAX_VERTS)
-    return snprintf(err, n, "bad poly_start"), 1;
-  for (int p = 0; p < cfg->n_polys; ++p)
-    if (cfg->poly_start[p + 1] - cfg->poly_start[p] < 3) return snprintf(err, n, "polygon %d has < 3 vertices", p), 1;
-  if (cfg->sbmpc_dt <= 0 || cfg->sbmpc_tf / cfg->sbmpc_dt > 4096) return snprintf(err, n, "bad sbmpc horizon"), 1;
-  return 0;
+  return config_host::default_config(kind, machinery, collav, time_step, cfg);
 }
 
 // message of this thread's last failed shipsim_create (shipsim_last_error(NULL)); set on every failing path
@@ -3564,187 +2367,62 @@ int shipsim_create(const shipsim_config* cfg_in, int32_t n_envs, int32_t n_obs_s
   h->cfg = *cfg_in;
   if (n_obs_ships > 0 && h->cfg.kind == SHIPSIM_KIND_AST) h->cfg.n_ships = 1 + n_obs_ships;
   const shipsim_config* cfg = &h->cfg;
-  if (validate(cfg, h->err, sizeof(h->err))) {
+  if (config_host::validate(cfg, h->err, sizeof(h->err))) {
     snprintf(g_create_err, sizeof(g_create_err), "%s", h->err);
     delete h;
     return SHIPSIM_EINVAL;
   }
+  *out = h;  // from here on a failure leaves the handle to the caller, with its message (shipsim_last_error)
   h->device = device;
   h->stream = (hipStream_t)stream;
   DeviceGuard g(device);
   h->lpe = launch_host::select(cfg->machinery, cfg->collav, cfg->n_ships, lanes_per_env(cfg, n_envs, device), false,
                                false, launch_host::kStep).lpe;
   h->lpe_uniform = h->lpe;
-  Params& P = h->P;
-  memset(&P, 0, sizeof(P));
-  P.epw = cfg->envs_per_wave;  // performance knob (0 = full waves; results identical)
+  // the host half (shipsim_config_host.hpp): parameters, per-ship constants, the constant block with the map grid
+  config_host::params(cfg, n_envs, h->P);
   const int ns = cfg->n_ships;
   ShipConst sc[SHIPSIM_MAX_SHIPS];
   memset(sc, 0, sizeof(sc));
-  for (int i = 0; i < ns; ++i) make_ship_const(cfg, &cfg->ship[i], &sc[i]);
-  P.kind = cfg->kind;
-  P.machinery = cfg->machinery;
-  P.collav = cfg->collav;
-  P.n_ships = ns;
-  P.max_sampling = cfg->max_sampling_frequency;
-  P.n_envs = n_envs;
-  P.n_polys = cfg->n_polys;
-  P.dt = cfg->time_step;
-  P.sim_time = cfg->simulation_time;
-  P.mach_dt_init = cfg->time_step;
-  P.mach_dt_reset = cfg->machinery_dt_quirk ? 0.01 : cfg->time_step;
-  P.vc_n = cfg->current_velocity_component_from_north;
-  P.vc_e = cfg->current_velocity_component_from_east;
-  P.wind_dir = cfg->wind_direction;
-  P.wind_speed = cfg->wind_speed;
-  P.roa2 = cfg->env_radius_of_acceptance * cfg->env_radius_of_acceptance;
-  P.sbmpc_tf = cfg->sbmpc_tf;
-  P.sbmpc_nsamp = (int32_t)(cfg->sbmpc_tf / cfg->sbmpc_dt);
-  P.sbmpc_dt = cfg->sbmpc_dt;
-  P.wind_sin = sin(cfg->wind_direction);
-  P.wind_cos = cos(cfg->wind_direction);
-  P.action_low = cfg->action_low;
-  P.action_high = cfg->action_high;
-  P.normalize_action = cfg->normalize_action;
-  if (ns >= 2) {  // init_get_intermediate_waypoints env.py:143-161 (ship 1 samples)
-    const shipsim_ship_config* o = &cfg->ship[1];
-    double ABn = o->route_north[o->n_route - 1] - o->route_north[0];
-    double ABe = o->route_east[o->n_route - 1] - o->route_east[0];
-    int msf = cfg->max_sampling_frequency;
-    double AB_length = sqrt(ABn * ABn + ABe * ABe);
-    P.AB_seg = AB_length / (msf + 1);
-    P.AB_seg_n = ABn / (msf + 1);
-    P.AB_seg_e = ABe / (msf + 1);
-    double AB_alpha = atan2(ABe, ABn);
-    double AB_beta = M_PI / 2 - AB_alpha;
-    P.omega_iw = M_PI / 2 - AB_beta;
-    P.iw_cos = cos(P.omega_iw);  // np.cos / np.sin of the scalar omega (env.py:226-227): glibc, as NumPy
-    P.iw_sin = sin(P.omega_iw);
-    P.n_base0 = P.AB_seg_n + o->route_north[0];
-    P.e_base0 = P.AB_seg_e + o->route_east[0];
-    P.initial_states[0] = (float)cfg->ship[0].initial_north_position_m;
-    P.initial_states[1] = (float)cfg->ship[0].initial_east_position_m;
-    P.initial_states[2] = 0.0f;
-    P.initial_states[3] = (float)o->initial_north_position_m;
-    P.initial_states[4] = (float)o->initial_east_position_m;
-    P.initial_states[5] = (float)o->initial_yaw_angle_rad;
-    P.initial_states[6] = 0.0f;
-    P.initial_states[7] = (float)o->initial_forward_speed_m_per_s;
-  }
-  // map
-  int nv = cfg->poly_start[cfg->n_polys];
-  double mn_e = cfg->poly_east[0], mx_e = mn_e, mn_n = cfg->poly_north[0], mx_n = mn_n;
-  for (int i = 0; i < nv; ++i) {
-    if (cfg->poly_east[i] < mn_e) mn_e = cfg->poly_east[i];
-    if (cfg->poly_east[i] > mx_e) mx_e = cfg->poly_east[i];
-    if (cfg->poly_north[i] < mn_n) mn_n = cfg->poly_north[i];
-    if (cfg->poly_north[i] > mx_n) mx_n = cfg->poly_north[i];
-  }
-  P.min_east = mn_e; P.max_east = mx_e; P.min_north = mn_n; P.max_north = mx_n;
-
-  // constant block: edges | boxes | config routes | grid (ConstBuf layout)
-  const bool use_grid = nv <= 64 && nv > 0 && cfg->map_query == SHIPSIM_MAP_GRID;
-  const int gnx = use_grid ? (int)ceil((mx_e - mn_e + 2 * kGridPad) / kGridCell) : 0;
-  const int gny = use_grid ? (int)ceil((mx_n - mn_n + 2 * kGridPad) / kGridCell) : 0;
-  const size_t gcells = (size_t)gnx * gny;
-  const size_t grid_off = (ConstBuf::kBytes + 255) & ~(size_t)255;
-  const size_t part_off = (grid_off + gcells * (sizeof(uint64_t) + 1) + 7) & ~(size_t)7;
-  size_t cbytes = part_off + gcells * 8 * sizeof(uint64_t);
-  char* hostc = (char*)calloc(1, cbytes);
-  Edge* E = (Edge*)hostc;
-  PolyBox* B = (PolyBox*)(hostc + sizeof(Edge) * SHIPSIM_MAX_VERTS);
-  double* R = (double*)(hostc + sizeof(Edge) * SHIPSIM_MAX_VERTS + sizeof(PolyBox) * SHIPSIM_MAX_POLYS);
-  for (int p = 0; p < cfg->n_polys; ++p) {
-    int s0 = cfg->poly_start[p], cnt = cfg->poly_start[p + 1] - s0;
-    B[p].first = s0;
-    B[p].count = cnt;
-    B[p].minx = B[p].maxx = cfg->poly_east[s0];
-    B[p].miny = B[p].maxy = cfg->poly_north[s0];
-    for (int i = 0; i < cnt; ++i) {
-      int j = (i + 1 == cnt) ? 0 : i + 1;
-      E[s0 + i].ax = cfg->poly_east[s0 + i];
-      E[s0 + i].ay = cfg->poly_north[s0 + i];
-      E[s0 + i].bx = cfg->poly_east[s0 + j];
-      E[s0 + i].by = cfg->poly_north[s0 + j];
-      if (E[s0 + i].ax < B[p].minx) B[p].minx = E[s0 + i].ax;
-      if (E[s0 + i].ax > B[p].maxx) B[p].maxx = E[s0 + i].ax;
-      if (E[s0 + i].ay < B[p].miny) B[p].miny = E[s0 + i].ay;
-      if (E[s0 + i].ay > B[p].maxy) B[p].maxy = E[s0 + i].ay;
-    }
-  }
-  for (int s = 0; s < ns; ++s)
-    for (int i = 0; i < cfg->ship[s].n_route; ++i) {
-      R[s * kMaxRoute + i] = cfg->ship[s].route_north[i];
-      R[SHIPSIM_MAX_SHIPS * kMaxRoute + s * kMaxRoute + i] = cfg->ship[s].route_east[i];
-    }
-  memcpy(hostc + ConstBuf::kShipsOff, sc, sizeof(ShipConst) * SHIPSIM_MAX_SHIPS);
-  if (use_grid) {
-    build_grid(E, nv, B, cfg->n_polys, mn_e - kGridPad, mn_n - kGridPad, gnx, gny, (uint64_t*)(hostc + grid_off),
-               (uint8_t*)(hostc + grid_off + gcells * sizeof(uint64_t)));
-    const uint64_t* gm = (const uint64_t*)(hostc + grid_off);
-    uint64_t* gp = (uint64_t*)(hostc + part_off);
-    for (size_t c = 0; c < gcells; ++c) {
-      int rank = 0;
-      for (int k = 0; k < 64; ++k)
-        if (gm[c] >> k & 1) gp[c * 8 + (rank++ & 7)] |= (uint64_t)1 << k;
-    }
-  }
-  hipError_t e = hipMalloc(&h->const_block, cbytes);
+  for (int i = 0; i < ns; ++i) config_host::ship_const(&cfg->ship[i], &sc[i]);
+  config_host::ConstBlock cb;
+  if (!config_host::const_block(cfg, sc, cb))
+    return fail(h, SHIPSIM_ENOMEM, "shipsim_create: out of host memory (constant block, %zu B)", cb.bytes);
+  hipError_t e = hipMalloc(&h->const_block, cb.bytes);
   if (e != hipSuccess) {
-    free(hostc);
-    int rc = fail(h, SHIPSIM_EHIP, "hipMalloc(const): %s", hipGetErrorString(e));
-    *out = h;
-    return rc;
+    free(cb.host);
+    return fail(h, SHIPSIM_EHIP, "hipMalloc(const): %s", hipGetErrorString(e));
   }
-  e = hipMemcpy(h->const_block, hostc, cbytes, hipMemcpyHostToDevice);
-  free(hostc);
-  if (e != hipSuccess) {
-    *out = h;
-    return fail(h, SHIPSIM_EHIP, "hipMemcpy(const): %s", hipGetErrorString(e));
-  }
-  h->K.base = (const char*)h->const_block;
-  h->K.n_edges = nv;
-  h->K.gnx = gnx;
-  h->K.gny = gny;
-  h->K.gx0 = mn_e - kGridPad;
-  h->K.gy0 = mn_n - kGridPad;
-  h->K.ginv = 1.0 / kGridCell;
-  h->K.grid_mask = use_grid ? (const uint64_t*)((const char*)h->const_block + grid_off) : nullptr;
-  h->K.grid_flag = use_grid ? (const uint8_t*)((const char*)h->const_block + grid_off + gcells * sizeof(uint64_t))
-                            : nullptr;
-  h->K.grid_part = use_grid ? (const uint64_t*)((const char*)h->const_block + part_off) : nullptr;
+  e = hipMemcpy(h->const_block, cb.host, cb.bytes, hipMemcpyHostToDevice);
+  free(cb.host);
+  if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "hipMemcpy(const): %s", hipGetErrorString(e));
+  const char* kb = (const char*)h->const_block;
+  const size_t flag_off = cb.grid_off + (size_t)cb.gnx * cb.gny * sizeof(uint64_t);
+  h->K.base = kb; h->K.n_edges = cb.n_edges; h->K.gnx = cb.gnx; h->K.gny = cb.gny;
+  h->K.gx0 = cb.gx0; h->K.gy0 = cb.gy0; h->K.ginv = 1.0 / config_host::kGridCell;
+  h->K.grid_mask = cb.use_grid ? (const uint64_t*)(kb + cb.grid_off) : nullptr;
+  h->K.grid_flag = cb.use_grid ? (const uint8_t*)(kb + flag_off) : nullptr;
+  h->K.grid_part = cb.use_grid ? (const uint64_t*)(kb + cb.part_off) : nullptr;
 
   // state block (DevState layout: ship arrays | routes | env arrays)
   const size_t S = (size_t)n_envs * ns;
   const state_host::Layout lay = state_host::layout(n_envs, ns);
-  h->S.ship_stride = lay.ship_stride;
-  h->S.route_stride = lay.route_stride;
-  h->S.env_stride = lay.env_stride;
-  h->S.env_off = lay.env_off;
+  h->S.ship_stride = lay.ship_stride; h->S.route_stride = lay.route_stride;
+  h->S.env_stride = lay.env_stride; h->S.env_off = lay.env_off;
   size_t bytes = (size_t)lay.bytes;
   e = hipMalloc(&h->dev_block, bytes);
-  if (e != hipSuccess) {
-    *out = h;
-    return fail(h, SHIPSIM_EHIP, "hipMalloc(state %zu B): %s", bytes, hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "hipMalloc(state %zu B): %s", bytes, hipGetErrorString(e));
   h->dev_bytes = bytes;
   h->S.base = (char*)h->dev_block;
   e = hipMalloc(&h->nonfinite_dev, sizeof(int32_t));
-  if (e != hipSuccess) {
-    *out = h;
-    return fail(h, SHIPSIM_EHIP, "hipMalloc(counter): %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "hipMalloc(counter): %s", hipGetErrorString(e));
   h->S.nonfinite = h->nonfinite_dev;
   (void)hipMemsetAsync(h->nonfinite_dev, 0, sizeof(int32_t), h->stream);
   e = hipMemsetAsync(h->dev_block, 0, bytes, h->stream);
-  if (e != hipSuccess) {
-    *out = h;
-    return fail(h, SHIPSIM_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
   int threads = 256, blocks = (int)((S + threads - 1) / threads);
   hipLaunchKernelGGL(init_kernel, dim3(blocks), dim3(threads), 0, h->stream, h->P, h->S, h->K);
   e = hipGetLastError();
-  *out = h;
   if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "init_kernel: %s", hipGetErrorString(e));
   return SHIPSIM_OK;
 }
@@ -4206,4 +2884,3 @@ int shipsim_diag_lane_faults(uint32_t* out32) {
 }
 
 }  // extern "C"
-#endif  // SHIPSIM_TU != 2

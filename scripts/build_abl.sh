@@ -3,7 +3,7 @@
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd); D=$R/ast_sac_amd/lib/abl; mkdir -p $D
 F="-O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -std=c++17 -I$R/include -I$R/ast_sac_amd/csrc"
-S=$R/ast_sac_amd/csrc/shipsim_kernels.hip
+S=$(cd $R && for f in $(python3 -c 'from ast_sac_amd.build_hash import OBJECTS; print(" ".join(s for s, _ in OBJECTS["shipsim"]))'); do echo $R/$f; done)  # every .hip file of the library
 
 /opt/rocm/bin/hipcc $F -mllvm -amdgpu-sched-strategy=iterative-ilp -DSHIPSIM_SRC_HASH='"abl-ilp"' $S -o $D/lib_ilp.so &
 wait

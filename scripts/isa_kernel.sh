@@ -2,9 +2,11 @@
 # Usage: bash scripts/isa_kernel.sh MANGLED_PREFIX [extra hipcc flags, e.g. -DSHIPSIM_REGCHECK=2]
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
+# the product's flags with object 1's set, and every .hip file of the library (ast_sac_amd/build_hash.py)
+F="$(cd $R && python3 -c 'from ast_sac_amd.build_hash import HIPFLAGS, lib_flag_sets; print(" ".join(HIPFLAGS + lib_flag_sets("shipsim")[0]))')"
+S=$(cd $R && for f in $(python3 -c 'from ast_sac_amd.build_hash import OBJECTS; print(" ".join(s for s, _ in OBJECTS["shipsim"]))'); do echo $R/$f; done)
 mkdir -p /tmp/rc && cd /tmp/rc
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -std=c++17 -I$R/include -I$R/ast_sac_amd/csrc \
-  -mllvm -disable-machine-licm -mllvm -amdgpu-sched-strategy=max-ilp -mllvm -amdgpu-use-amdgpu-trackers --save-temps "${@:2}" $R/ast_sac_amd/csrc/shipsim_kernels.hip -o /tmp/rc/x.so 2>/dev/null
+/opt/rocm/bin/hipcc $F -I$R/include -I$R/ast_sac_amd/csrc --save-temps "${@:2}" $S -o /tmp/rc/x.so 2>/dev/null
 python3 - "$1" <<'PY'
 import sys
 L = open('/tmp/rc/shipsim_kernels-hip-amdgcn-amd-amdhsa-gfx950.s').read().split('\n')

@@ -15,6 +15,9 @@ if [ "$N" = sac ]; then
   python3 scripts/regsummary.py /tmp/regcheck_sac.txt
   exit 0
 fi
-/opt/rocm/bin/hipcc $FLAGS -mllvm -disable-machine-licm -mllvm -amdgpu-sched-strategy=max-ilp -mllvm -amdgpu-use-amdgpu-trackers -DSHIPSIM_REGCHECK=$N -Rpass-analysis=kernel-resource-usage "$@" \
-  ast_sac_amd/csrc/shipsim_kernels.hip -o /tmp/regcheck.so 2> /tmp/regcheck.txt
+# object 1's flag set and every .hip file of the library (ast_sac_amd/build_hash.py)
+LF="$(python3 -c 'from ast_sac_amd.build_hash import lib_flag_sets; print(" ".join(lib_flag_sets("shipsim")[0]))')"
+S="$(python3 -c 'from ast_sac_amd.build_hash import OBJECTS; print(" ".join(s for s, _ in OBJECTS["shipsim"]))')"
+/opt/rocm/bin/hipcc $FLAGS $LF -DSHIPSIM_REGCHECK=$N -Rpass-analysis=kernel-resource-usage "$@" \
+  $S -o /tmp/regcheck.so 2> /tmp/regcheck.txt
 python3 scripts/regsummary.py /tmp/regcheck.txt | grep -E "ast_step|sbmpc_eval|legacy"

@@ -9,15 +9,15 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from __graft_entry__ import HIPCC, HIPFLAGS, SAC_SRC, SRC  # noqa: E402
-from ast_sac_amd.build_hash import lib_flag_sets  # noqa: E402
+from __graft_entry__ import HIPCC, HIPFLAGS  # noqa: E402
+from ast_sac_amd.build_hash import lib_objects  # noqa: E402
 
 
-def report(name, src):
+def report(name):
     err = ""
-    for i, flags in enumerate(lib_flag_sets(name)):  # every object of the library with its own flags
-        cmd = [HIPCC] + HIPFLAGS + flags + ["-Rpass-analysis=kernel-resource-usage"] + src + \
-            ["-o", f"/tmp/regreport_{name}_{i}.so"]
+    for i, (src, flags) in enumerate(lib_objects(name)):  # every object of the library: its source, its own flags
+        cmd = [HIPCC] + HIPFLAGS + flags + ["-Rpass-analysis=kernel-resource-usage", os.path.join(ROOT, src),
+                                            "-o", f"/tmp/regreport_{name}_{i}.so"]
         err += subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     rows, cur = {}, None
     for line in err.splitlines():
@@ -39,9 +39,9 @@ def report(name, src):
 def main():
     spill = []
     total = 0
-    for name, src in (("shipsim", SRC), ("sacfused", SAC_SRC)):
+    for name in ("shipsim", "sacfused"):
         print(f"== lib{name}.so ==")
-        for dn, v in report(name, src):
+        for dn, v in report(name):
             total += 1
             s, vs = v.get("SGPRs Spill", 0), v.get("VGPRs Spill", 0)
             print(f"{dn}\n    VGPR {v.get('VGPRs')} AGPR {v.get('AGPRs')} SGPR {v.get('TotalSGPRs')} sgpr_spill {s} "

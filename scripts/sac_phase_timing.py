@@ -24,11 +24,11 @@ def diag_path(variant=None):
 
 def build(variant=None, flags=()):
     sys.path.insert(0, ROOT)
-    from __graft_entry__ import HIPCC, HIPFLAGS, SAC_SRC
-    from ast_sac_amd.build_hash import LIB_FLAGS
+    from __graft_entry__ import HIPCC, HIPFLAGS
+    from ast_sac_amd.build_hash import LIB_FLAGS, OBJECTS
     os.makedirs(os.path.dirname(DIAG), exist_ok=True)
     subprocess.check_call([HIPCC] + HIPFLAGS + LIB_FLAGS["sacfused"] + ["-mllvm", "-amdgpu-sched-strategy=max-ilp"] + ["-DSACF_PHASE_TIMING", '-DSACF_SRC_HASH="diag"']
-                          + list(flags) + SAC_SRC + ["-o", diag_path(variant)])
+                          + list(flags) + [os.path.join(ROOT, OBJECTS["sacfused"][0][0]), "-o", diag_path(variant)])
     print("built", diag_path(variant))
 
 
