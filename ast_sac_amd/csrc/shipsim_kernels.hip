@@ -2720,6 +2720,19 @@ int shipsim_fork(shipsim_handle* h, const void* from, int64_t bytes, const int32
   return SHIPSIM_OK;
 }
 
+// the splitting level of shipsim_resample's callers (the kernel is shipsim_resample.hip's)
+int shipsim_level_distance(shipsim_handle* h, double* out) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (!out) return fail(h, SHIPSIM_EINVAL, "level_distance: the output is NULL");
+  if (h->P.kind != SHIPSIM_KIND_AST && h->P.kind != SHIPSIM_KIND_NONIW)
+    return fail(h, SHIPSIM_EINVAL, "level_distance: a single-ship handle has no obstacle ship to measure to");
+  if (!h->ever_reset) return fail(h, SHIPSIM_ESTATE, "level_distance before reset");
+  DeviceGuard g(h->device);
+  shipsim_level_distance_launch(h->stream, h->S, h->P.n_envs, h->P.n_ships, out);
+  HIPCHK(h, hipGetLastError());
+  return SHIPSIM_OK;
+}
+
 int shipsim_set_trajectory(shipsim_handle* h, double* ship_rows, double* env_rows, int32_t capacity,
                            int32_t* lengths) {
   if (!h || !h->dev_block) return SHIPSIM_EINVAL;

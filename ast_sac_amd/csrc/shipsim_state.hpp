@@ -133,3 +133,6 @@ __device__ __forceinline__ const ShipConst* stage_consts(const ConstBuf& K, Ship
 
 // single_tick_pipe_kernel<POW2_DT> on `blocks` blocks of 192 threads (shipsim_c2_pipe.hip)
 void shipsim_c2_pipe_launch(int blocks, hipStream_t st, const Params& P, const DevState& S, const ConstBuf& K, int k);
+
+// level_distance_kernel over n_envs envs of n_ships ships (shipsim_resample.hip)
+void shipsim_level_distance_launch(hipStream_t st, const DevState& S, int n_envs, int n_ships, double* out);

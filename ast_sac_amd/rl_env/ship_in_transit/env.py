@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from ... import shipsim_abi as abi
-from ...shipsim import ShipSim
+from ...shipsim import ShipSim, resample
 from ...spaces import Box
 from .trajectory import EpisodeRecord, RewardTracker, ShipSnapshots
 
@@ -141,6 +141,26 @@ class BatchedMultiShipRLEnv:
         for x in (ep_idx, dec_idx, log_len):
             if x is not None:
                 x.copy_(x[idx])
+
+    # -- weighted splitting (beyond the reference; shipsim.resample) --
+    def level_distance(self, out=None):
+        """Per env, the own ship's distance to the nearest obstacle ship: (n_envs,) float64 on the device."""
+        return self.sim.level_distance(out=out)
+
+    def split(self, weight, potential, seed, counter, ep_idx, dec_idx, log_len=None, weather="keep"):
+        """One splitting step on the device: the envs are resampled in proportion to weight * potential, in place
+        (shipsim.resample: a selected env keeps its slot, further clones of it fill the slots of the envs that were
+        not selected), the caller's stream arrays are gathered (fork_stream_state) and the envs forked. Returns
+        (src, weight, total, status) as resample does: clone j carries weight[j], and sum_j weight[j] f(env j) after
+        the call is an unbiased estimate of sum_i weight_in[i] f(env i) before it. Without usable mass (status 1 or
+        2) src is the identity and nothing moves. counter: (1,) int64 device tensor, read; the caller advances it.
+        With weather="keep" (what the in-place arrangement is for: a survivor's weather never changes under it)
+        nothing is copied to the host and the whole step can be captured into a graph; "follow" is fork()'s
+        host-side weather move."""
+        src, w, total, status = resample(weight, potential, seed, counter, arrangement="in_place")
+        self.fork_stream_state(src, ep_idx, dec_idx, log_len)
+        self.fork(src, weather=weather)
+        return src, w, total, status
 
     # -- reference helpers (env.py:186-196) --
     def do_normalize_action(self, a_real):

@@ -72,11 +72,14 @@ def load_library(path=LIB_PATH):
                            ("shipsim_state_bytes", [P]),
                            ("shipsim_snapshot", [P, P, C.c_int64]),
                            ("shipsim_restore", [P, P, C.c_int64]),
-                           ("shipsim_fork", [P, P, C.c_int64, P])):
+                           ("shipsim_fork", [P, P, C.c_int64, P]),
+                           ("shipsim_resample_workspace_bytes", [C.c_int32]),
+                           ("shipsim_resample", [C.c_int32, P, P, C.c_uint64, P, C.c_int32, P, C.c_int64, P, P, P, P, P]),
+                           ("shipsim_level_distance", [P, P])):
         try:
             getattr(L, name).argtypes = argtypes
-            if name == "shipsim_state_bytes":
-                L.shipsim_state_bytes.restype = C.c_int64
+            if name in ("shipsim_state_bytes", "shipsim_resample_workspace_bytes"):
+                getattr(L, name).restype = C.c_int64
         except AttributeError:
             if "SHIPSIM_LIB" not in os.environ:
                 raise
@@ -98,7 +101,8 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_nonfinite_count", "shipsim_lanes_per_env", "shipsim_set_stream",
                     "shipsim_run_policy", "shipsim_diag_lane_faults", "shipsim_set_stream_tail", "shipsim_div_check",
                     "shipsim_sbmpc_eval_multi", "shipsim_set_weather", "shipsim_get_weather",
-                    "shipsim_state_bytes", "shipsim_snapshot", "shipsim_restore", "shipsim_fork")
+                    "shipsim_state_bytes", "shipsim_snapshot", "shipsim_restore", "shipsim_fork",
+                    "shipsim_resample_workspace_bytes", "shipsim_resample", "shipsim_level_distance")
 
 
 class Snapshot:
@@ -384,6 +388,18 @@ class ShipSim:
         self._keep_fork = s
         return s
 
+    def level_distance(self, out=None):
+        """Per env, the own ship's distance to the nearest obstacle ship (shipsim_level_distance): an (n_envs,)
+        float64 device tensor, the level a splitting potential is built from. AST and NONIW handles, after a reset."""
+        if out is None:
+            out = torch.empty(self.n_envs, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous() \
+                or out.numel() != self.n_envs:
+            raise ShipSimError(f"level_distance: out must be a contiguous float64 tensor of {self.n_envs} on {self.device}")
+        self._follow_stream()
+        self._check(self.L.shipsim_level_distance(self.h, _ptr(out)), "shipsim_level_distance")
+        return out
+
     # -- per-env weather (include/shipsim.h: shipsim_set_weather) --
     WEATHER_KEYS = ("wind_speed", "wind_direction", "current_north", "current_east")
 
@@ -503,3 +519,57 @@ def sbmpc_eval_multi(requests, n_obs, tf=1000.0, dt=20.0, device="cuda"):
     if rc:
         raise ShipSimError(f"shipsim_sbmpc_eval_multi failed ({rc}): n_obs must be 1..{abi.MAX_OBS}")
     return out
+
+
+RESAMPLE_SORTED, RESAMPLE_IN_PLACE = 0, 1
+RESAMPLE_MAX_N = 1 << 22
+_ARRANGEMENTS = {"sorted": RESAMPLE_SORTED, "in_place": RESAMPLE_IN_PLACE}
+_resample_ws = {}  # (device, n) -> (workspace, total, status): one set per population size, reused by every call
+
+
+def resample(weight, potential, seed, counter, arrangement="in_place", out_src=None, out_weight=None):
+    """Systematic resampling of n envs in proportion to weight * potential (shipsim_resample): returns
+    (src int32, weight float64, total float64 (1,), status int32 (1,)), all on the device. src is what fork() takes;
+    weight[j] is what clone j carries so that sum_j weight[j] f(x[src[j]]) stays an unbiased estimate of
+    sum_i weight_in[i] f(x[i]); total is the mass the weights preserve; status 0, or 1 (no mass) / 2 (a negative or
+    non-finite mass) with src the identity and the weights as given. arrangement "in_place": an env that is selected
+    keeps its slot and further clones fill the slots of those that are not; "sorted": src non-decreasing.
+    counter: (1,) int64 device tensor read by the launch (the caller advances it between calls). Asynchronous on
+    the current stream and capturable; the workspace — and total and status, which the next call of the same size
+    overwrites — is cached per (device, n). out_weight may be weight."""
+    L = load_library()
+    w = torch.as_tensor(weight)
+    if not w.is_cuda:
+        raise ShipSimError("resample: weight must be a device tensor")
+    dev = w.device
+    w = w.to(torch.float64).contiguous().reshape(-1)
+    p = torch.as_tensor(potential, dtype=torch.float64, device=dev).contiguous().reshape(-1)
+    n = int(w.numel())
+    if p.numel() != n:
+        raise ShipSimError(f"resample: {n} weights and {p.numel()} potentials")
+    if not 1 <= n <= RESAMPLE_MAX_N:
+        raise ShipSimError(f"resample: n must be in 1..{RESAMPLE_MAX_N}, not {n}")
+    if arrangement not in _ARRANGEMENTS:
+        raise ShipSimError(f"resample: arrangement must be 'in_place' or 'sorted', not {arrangement!r}")
+    if counter.dtype != torch.int64 or counter.device != dev or counter.numel() < 1:
+        raise ShipSimError("resample: counter must be an int64 device tensor")
+    for name, t, dt in (("out_src", out_src, torch.int32), ("out_weight", out_weight, torch.float64)):
+        if t is not None and (t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() != n):
+            raise ShipSimError(f"resample: {name} must be a contiguous {dt} tensor of {n} on {dev}")
+    key = (dev.index, n)
+    if key not in _resample_ws:
+        need = int(L.shipsim_resample_workspace_bytes(n))
+        _resample_ws[key] = (torch.empty(need, dtype=torch.uint8, device=dev),
+                             torch.zeros(1, dtype=torch.float64, device=dev),
+                             torch.zeros(1, dtype=torch.int32, device=dev))
+    ws, total, status = _resample_ws[key]
+    src = out_src if out_src is not None else torch.empty(n, dtype=torch.int32, device=dev)
+    wout = out_weight if out_weight is not None else torch.empty(n, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        rc = L.shipsim_resample(n, _ptr(w), _ptr(p), int(seed) & ((1 << 64) - 1), _ptr(counter),
+                                _ARRANGEMENTS[arrangement], _ptr(ws), ws.numel(), _ptr(src), _ptr(wout), _ptr(total),
+                                _ptr(status), C.c_void_p(stream.cuda_stream))
+    if rc:
+        raise ShipSimError(f"shipsim_resample failed ({rc})")
+    return src, wout, total, status

@@ -29,7 +29,8 @@ extern "C" {
 
 #define SHIPSIM_ABI_VERSION 12  /* 12: shipsim_set_weather / shipsim_get_weather (per-env wind and current) */
 /* (shipsim_state_bytes / shipsim_snapshot / shipsim_restore / shipsim_fork came later and are additive: no struct
- * layout and no existing call changed, so the version stays 12; a binding looks the four symbols up on their own) */
+ * layout and no existing call changed, so the version stays 12; a binding looks the four symbols up on their own;
+ * likewise shipsim_resample_workspace_bytes / shipsim_resample / shipsim_level_distance after them) */
 
 #define SHIPSIM_MAX_ROUTE 16   /* waypoints per ship route (obs ship: 2 + max_sampling_frequency) */
 #define SHIPSIM_MAX_POLYS 16   /* land polygons in the map */
@@ -349,6 +350,54 @@ int64_t shipsim_state_bytes(const shipsim_handle* h);
 int shipsim_snapshot(shipsim_handle* h, void* dst, int64_t bytes);
 int shipsim_restore(shipsim_handle* h, const void* src, int64_t bytes);
 int shipsim_fork(shipsim_handle* h, const void* from, int64_t bytes, const int32_t* src_env);
+
+/* ---- weighted splitting: resample a population of envs in proportion to weight x potential -----------------
+ * shipsim_resample turns n weights and n potentials into the index array a shipsim_fork takes and the weights the
+ * clones carry, such that sum_j weight_out[j] * f(x[src_out[j]]) is an unbiased estimate of sum_i weight[i] * f(x[i])
+ * for any potential > 0 (systematic resampling). It is stateless like shipsim_sbmpc_eval_multi: no handle, device
+ * pointers, asynchronous on `stream`, no host synchronisation and no allocation, so it can be captured into a graph
+ * next to shipsim_fork. Everything it keeps between its launches lives in `workspace`, a caller-owned device buffer
+ * of at least shipsim_resample_workspace_bytes(n) bytes, 16-byte aligned (contents undefined before and after).
+ * weight_out may be weight. *counter is read by the launch and not changed, as in shipsim_run_policy.
+ *
+ * The arithmetic is in integers, so that any association order of the scans — and the restatement in
+ * tests/resample_ref.py — gives the same bits (ast_sac_amd/csrc/shipsim_resample_host.hpp):
+ *   mass      p_i = weight[i] * potential[i] (one IEEE multiply); m = max_i p_i.
+ *             *status_out = 2 if any p_i is negative or not finite, 1 if m == 0; then src_out[j] = j,
+ *             weight_out = weight, *total_out = 0: defined behaviour, nothing to check on the host. 0 otherwise.
+ *   quantise  m = f * 2^e with f in [0.5, 1) (frexp): q_i = (uint64) ceil(ldexp(p_i, 40 - e)), so q_i >= 1 exactly
+ *             when p_i > 0 and the largest is in [2^39, 2^40].
+ *   scan      C_i = q_0 + ... + q_i in uint64; Q = C_{n-1} <= 2^62.
+ *   offset    one Philox4x32-10 block keyed by seed {lo, hi} on the counter words {*counter lo, *counter hi,
+ *             0x52455341, 0} gives c0..c3; U = ((c0 | c1 << 32) * 2^64 + (c2 | c3 << 32)) mod Q.
+ *   positions t_j = floor((j * Q + U) / n), formed as j * s + (j * r + U) / n with Q = s * n + r; sel[j] = the
+ *             smallest i with C_i > t_j. Env i is selected floor(n q_i / Q) or ceil(n q_i / Q) times, n q_i / Q in
+ *             the mean over U.
+ *   arrange   SHIPSIM_RESAMPLE_SORTED: src_out = sel. SHIPSIM_RESAMPLE_IN_PLACE: every selected env keeps its slot
+ *             (src_out[i] = i); its further clones, in increasing source order, fill the slots of the envs that
+ *             were not selected, in increasing slot order — a survivor never moves, so it keeps its slot's weather,
+ *             noise and table columns, and shipsim_fork leaves it untouched.
+ *   weights   weight_out[j] = weight[s] * ((double)Q / ((double)n * (double)q_s)), s = src_out[j] (conversions to
+ *             nearest, three IEEE operations, no contraction); *total_out = ldexp((double)Q, e - 40), the total
+ *             mass the weights preserve: in [sum p, sum p * (1 + n * 2^-39)].
+ * total_out and status_out may be NULL. SHIPSIM_EINVAL, before any device call: n < 1 or n >
+ * SHIPSIM_RESAMPLE_MAX_N; a NULL weight, potential, counter, workspace, src_out or weight_out; an arrangement other
+ * than the two; workspace_bytes too small or a workspace not 16-byte aligned. shipsim_resample_workspace_bytes gives
+ * SHIPSIM_EINVAL for such an n and does not decrease with n.
+ *
+ * shipsim_level_distance writes, per env, min over the obstacle ships k = 1..K of sqrt(dn * dn + de * de) with
+ * dn = north[0] - north[k], de = east[0] - east[k] (n_envs doubles on the device, asynchronous on the handle's
+ * stream): the level a distance-based potential is built from, as the plain expression, so that it has the bits of
+ * the same expression on shipsim_get_state's values. AST handles with K = 1..4 and NONIW handles; SHIPSIM_EINVAL on
+ * a SINGLE handle or a NULL out, SHIPSIM_ESTATE before the first reset (the reason in shipsim_last_error). */
+#define SHIPSIM_RESAMPLE_SORTED 0
+#define SHIPSIM_RESAMPLE_IN_PLACE 1
+#define SHIPSIM_RESAMPLE_MAX_N (1 << 22)
+int64_t shipsim_resample_workspace_bytes(int32_t n);
+int shipsim_resample(int32_t n, const double* weight, const double* potential, uint64_t seed, const int64_t* counter,
+                     int32_t arrangement, void* workspace, int64_t workspace_bytes, int32_t* src_out,
+                     double* weight_out, double* total_out, int32_t* status_out, void* stream);
+int shipsim_level_distance(shipsim_handle* h, double* out);
 
 /* ---- trajectory recording (f1: simulation_results export) ----------------------------------
  * Per-tick rows of ShipModelAST/SimpleShipModel.store_simulation_data (ship_model.py:903-957,
