@@ -619,7 +619,9 @@ __device__ __forceinline__ void tanh_normal(float mean, float ls_raw, float eps,
 }
 
 // one batch item (replay sample or given batch) and its two reparameterisation normals; padding rows
-// (item >= B) read a valid row and draw zero noise
+// (item >= B) read a valid row — a draw of their own when sampled, else row B - 1 — with zero noise from a caller's
+// eps and normals of their own from the in-kernel stream: every consumer masks rows >= B (P3's s0 = s1 = 0, the
+// scalar block's r >= B), so neither reaches a loss or a gradient sum (tests/test_gpu_sac_draw.py)
 __device__ __forceinline__ int64_t batch_item(const MArgs& a, int item, float& e0, float& e1) {
   const int B = a.L.B;
   const bool pad = item >= B;

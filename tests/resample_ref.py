@@ -21,7 +21,12 @@ def tile():
 
 def philox(c0, c1, c2, c3, k0, k1):
     """Philox4x32-10 on one counter block (tests/test_gpu_run_policy.py's, on scalars)."""
-    c = [np.uint64(x) for x in (c0, c1, c2, c3)]
+    return [int(x) for x in philox_words(c0, c1, c2, c3, k0, k1)]
+
+
+def philox_words(c0, c1, c2, c3, k0, k1):
+    """The same rounds on numpy uint64 words: scalars, or arrays of counter blocks under one key."""
+    c = [np.asarray(x, dtype=np.uint64) for x in (c0, c1, c2, c3)]
     k0, k1 = np.uint64(k0), np.uint64(k1)
     m32 = np.uint64(0xFFFFFFFF)
     for _ in range(10):
@@ -32,7 +37,7 @@ def philox(c0, c1, c2, c3, k0, k1):
         c = [n0 & m32, p1 & m32, n2 & m32, p0 & m32]
         k0 = (k0 + np.uint64(0x9E3779B9)) & m32
         k1 = (k1 + np.uint64(0xBB67AE85)) & m32
-    return [int(x) for x in c]
+    return c
 
 
 def offset_bits(seed, counter):
