@@ -852,6 +852,16 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // work instead of in front of their first use. The sliced step kernels (MODE 0) keep the query as
   // it was: the tests' independent reference.
   constexpr bool EARLY_MAP = RC_PAR;
+  // The same streams run a flattened tick (profiles/tick_waits.md "The tick's control flow"): one
+  // `going` region from the pass's hand-out to the end of the tick body instead of a guard per section, with the
+  // lane exchanges inside it, and the decision ladder as selects. Every other instantiation keeps the guarded tick
+  // (the sliced step kernels: the tests' independent reference).
+  constexpr bool FLAT = RC_PAR;
+  // Legal because an env is exactly one 16-lane DPP row here and `going` is per env: every exchange after the pass
+  // (pair_swap, ship_reduce, ship_or, env_lane_*, the hull corners' shuffle by 4·SLOTS lanes) reads lanes of its own
+  // row, so inside one `if (going)` a source lane is active exactly when its destination is. (The SBMPC pass itself
+  // is wave-cooperative across envs and stays outside the region.)
+  static_assert(!FLAT || (LPE == 16 && SLOTS == 2), "the flat tick: env = one DPP row, going per env");
   using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
   // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
   // instantiation compiles to the code it had (the dead arm of a constant condition is not emitted)
@@ -1211,6 +1221,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     constexpr bool LOS_PRE = COLLAV == SHIPSIM_COLLAV_SBMPC && SLOTS == 2;  // the LOS term evaluated once per tick
     double los_pre_q = 0.0, los_pre_e = 0.0;
     bool sb_active = false;
+    double sb_pb = 1.0, sb_cb = 0.0;  // (FLAT) the pass's result, handed out inside the going region
     if (COLLAV == SHIPSIM_COLLAV_SBMPC && SLOTS > 2) {  // do_list of every obstacle ship (env.py:366-370)
       constexpr int NOB = SLOTS - 1 < SHIPSIM_MAX_OBS ? SLOTS - 1 : SHIPSIM_MAX_OBS;  // (slots past K duplicate a ship)
       SbMulti<NOB> in;
@@ -1269,6 +1280,18 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     } else if (COLLAV == SHIPSIM_COLLAV_SBMPC) {
       bool need = false;
       double los_arg = 0.0;
+      if constexpr (FLAT) {  // the flat tick: the two guards below as one
+        if (going) {
+          los_pre_q = los_q(c, s, s.n, s.e, los_pre_e);
+          if (is_test) {
+            s.e_ct = los_pre_e;
+            los_arg = los_windup(c, s, los_pre_q);
+            double d0 = pe - s.e, d1 = pn - s.n;
+            need = sqrt_lt(d0 * d0 + d1 * d1, 2000.0);  // D_INIT_
+            need = diag::sb_request(need, PT.max_sampling);
+          }
+        }
+      } else {
       if (going) {
         // the LOS cross-track term at this position, for every ship: its control below reuses it (its position
         // and segment are the same there unless the waypoint index advances)
@@ -1282,6 +1305,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         double d0 = pe - s.e, d1 = pn - s.n;
         need = sqrt_lt(d0 * d0 + d1 * d1, 2000.0);  // D_INIT_
         need = diag::sb_request(need, PT.max_sampling);  // (the product: need itself)
+      }
       }
       double pb = 1.0, cb = 0.0;
       int need0 = 0;
@@ -1306,18 +1330,31 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         need0 = env_lane_i<LPE, 0>((int)need, env_lane0);
       }
       sb_active = need0;
+      if constexpr (FLAT) {
+        sb_pb = pb; sb_cb = cb;
+      } else {
       if (opaque_if<OPQ>(going)) {  // (tested here, not held as a lane mask across the optimiser's loop)
         if (need0) { p_last = pb; chi_last = cb; }
         else { p_last = 1; chi_last = 0; }
         if (opaque_if<OPQ>(is_test ? 1 : 0) && need0) { sf = pb; off = cb; }
       }
+      }
     }
 
     PT_MARK(0);
+    // The flat tick: one `going` region from here to the end of the tick body (FLAT, above), its body's own guards
+    // constant-true. (Not re-indented: the body is every instantiation's.)
+    if (!FLAT || opaque_if<OPQ>(going)) {
+    if constexpr (FLAT) SHIPSIM_LANE_CHECK(LPE, 9);  // (diagnostics build: an env's whole row enters together)
+    if constexpr (FLAT && COLLAV == SHIPSIM_COLLAV_SBMPC) {  // the pass's hand-out
+      if (sb_active) { p_last = sb_pb; chi_last = sb_cb; }
+      else { p_last = 1; chi_last = 0; }
+      if (opaque_if<OPQ>(is_test ? 1 : 0) && sb_active) { sf = sb_pb; off = sb_cb; }
+    }
     // ---- ship ticks (test_step :345-445 / obs_step :447-536) ----
     double my_speed_out = 0.0, dtravel = 0.0, dtime = 0.0;
     double ep_n = 0.0, ep_e = 0.0, ep_dt = 0.0;  // (EARLY_MAP) the position after this tick's step, and the step
-    if (going) {
+    if (FLAT || going) {
       if constexpr (EARLY_MAP) {
         // The map query's cell and, where it changes, the cell's edge share and class, requested here: the query
         // needs only the position after the tick's Euler step, which the state at the tick's start fixes (a frozen
@@ -1377,7 +1414,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     // ---- own-ship map queries, split over the ship's sub-lanes ----
     double d2 = INFINITY;
     bool gr = false;
-    if (going) {
+    if (FLAT || going) {
       int cc;
       if constexpr (EARLY_MAP) {
         cc = g_cell;  // this position's cell, its share and class already requested (the top of the ship tick)
@@ -1438,7 +1475,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     const double my_ground = sqrt(d2);
     PT_MARK(2);
     bool my_end = false, my_outside = false, my_roa = false, my_nf = false;
-    if (going) {
+    if (FLAT || going) {
       my_end = sqrt_le((s.n - s.end_n) * (s.n - s.end_n) + (s.e - s.end_e) * (s.e - s.end_e), 200.0);
       double margin = c.l_ship / 2;
       my_outside = (s.n < PT.min_north + margin || s.n > PT.max_north - margin) ||
@@ -1493,7 +1530,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
 #undef NEAREST
       any_nf = nf & XF_NONFINITE;
     }
-    if (going) {
+    if (FLAT || going) {
       travel_dist += Odtravel;
       travel_time += Odtime;
       // next_states (env.py:582-591) and self.states
@@ -1599,6 +1636,22 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       ticks += 1;
       dec_ticks += 1;
       bool finish = nonfinite;
+      if constexpr (FLAT) {
+        // the ladder below as selects over the env's few ints (both sides of every rung are side-effect-free):
+        // phase 0: done finishes, else the RoA moves to phase 1 with an IW and finishes without; phase 1: finishes
+        // unless the last IW was sampled, which resets the travel tracker and (not done) moves to phase 2; phase 2:
+        // done finishes
+        const bool p0 = phase == 0, p1 = phase == 1;
+        const bool iw = opaque_if<OPQ>(have_iw) != 0;
+        const bool last_iw = sampling_count == PT.max_sampling;
+        const bool roa = roa_o && !combined_done;
+        const bool fin = p0 ? (combined_done || (roa && !iw)) : p1 ? (!last_iw || combined_done) : combined_done;
+        const bool clear = p1 && last_iw;
+        travel_dist = clear ? 0.0 : travel_dist;
+        travel_time = clear ? 0.0 : travel_time;
+        phase = (p0 && roa && iw) ? 1 : (clear && !combined_done) ? 2 : phase;
+        finish = finish || fin;
+      } else
       if (phase == 0) {
         const bool roa = roa_o;
         if (combined_done) finish = true;
@@ -1629,6 +1682,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       const int mt = OPQ ? opaque_v(budget) : budget;  // (OPQ: its test not held across the loop)
       going = opaque_if<OPQ>((!OPM_GET(ready) && (mt <= 0 || ticks < mt)) ? 1 : 0);
     }
+    }  // (the flat tick's going region)
     PT_MARK(3);
   }
   if (!CHAIN) break;
