@@ -32,6 +32,7 @@
 #include "shipsim_launch_host.hpp"   // the list of step kernels and the choice among them
 #include "shipsim_weather_host.hpp"  // shipsim_set_weather's host half
 #include "shipsim_state_host.hpp"    // the state block as a table of columns (snapshot / restore / fork)
+#include "shipsim_archive_host.hpp"  // shipsim_archive_store / _load's host half
 
 #include "shipsim_diag.hpp"  // diagnostics / ablation hooks (none in the product build)
 
@@ -2784,6 +2785,68 @@ int shipsim_level_distance(shipsim_handle* h, double* out) {
   DeviceGuard g(h->device);
   shipsim_level_distance_launch(h->stream, h->S, h->P.n_envs, h->P.n_ships, out);
   HIPCHK(h, hipGetLastError());
+  return SHIPSIM_OK;
+}
+
+// ---- the state archive: the state block of n_cells envs in the caller's memory (the kernel is shipsim_archive.hip's,
+// the checks and the arithmetic shipsim_archive_host.hpp's) ----
+int64_t shipsim_archive_bytes(const shipsim_handle* h, int32_t n_cells) {
+  if (!h || !h->dev_block || n_cells < 1 || n_cells > archive_host::kMaxCells) return SHIPSIM_EINVAL;
+  return archive_host::archive_bytes(n_cells, h->P.n_ships);
+}
+
+// what store and load refuse alike; on success the two tables: the live block's and the archive's
+static int archive_call_check(shipsim_handle* h, const char* what, const void* archive, int64_t bytes, int32_t n_cells,
+                              const void* index, const char* index_name, state_host::Table* live,
+                              state_host::Table* arch) {
+  switch (archive_host::check_args(archive, index, bytes, n_cells, h->P.n_ships)) {
+    case archive_host::kArgOk: break;
+    case archive_host::kArgNullArchive: return fail(h, SHIPSIM_EINVAL, "%s: the archive is NULL", what);
+    case archive_host::kArgNullIndex: return fail(h, SHIPSIM_EINVAL, "%s: %s is NULL", what, index_name);
+    case archive_host::kArgCells:
+      return fail(h, SHIPSIM_EINVAL, "%s: n_cells = %d, not in 1..%d (SHIPSIM_ARCHIVE_MAX_CELLS)", what, n_cells,
+                  archive_host::kMaxCells);
+    case archive_host::kArgBytes:
+      return fail(h, SHIPSIM_EINVAL, "%s: %lld bytes, an archive of %d cells of this handle has %lld "
+                  "(shipsim_archive_bytes)", what, (long long)bytes, n_cells,
+                  (long long)archive_host::archive_bytes(n_cells, h->P.n_ships));
+    case archive_host::kArgAlign: return fail(h, SHIPSIM_EINVAL, "%s: the archive is not 16-byte aligned", what);
+  }
+  if (h->T.ship)
+    return fail(h, SHIPSIM_EINVAL, "%s: trajectory recording is on (rows, lengths and fuel are not part of a snapshot)",
+                what);
+  const state_host::Layout lay = {h->S.ship_stride, h->S.route_stride, h->S.env_stride, h->S.env_off,
+                                  (int64_t)h->dev_bytes};
+  *live = state_host::table(lay, h->P.n_ships);
+  *arch = state_host::table(state_host::layout(n_cells, h->P.n_ships), h->P.n_ships);
+  const int64_t most = h->P.n_envs > n_cells ? h->P.n_envs : n_cells;
+  if (state_host::max_units(*live, most) > archive_host::kMaxUnits)
+    return fail(h, SHIPSIM_EINVAL, "%s: %lld slots are more than the gather counts", what, (long long)most);
+  return SHIPSIM_OK;
+}
+
+int shipsim_archive_store(shipsim_handle* h, void* archive, int64_t bytes, int32_t n_cells, const int32_t* env_of_cell) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  state_host::Table live, arch;
+  if (int rc = archive_call_check(h, "archive_store", archive, bytes, n_cells, env_of_cell, "env_of_cell", &live, &arch))
+    return rc;
+  if (!h->ever_reset) return fail(h, SHIPSIM_ESTATE, "archive_store before reset");
+  DeviceGuard g(h->device);
+  shipsim_archive_gather_launch(h->stream, live, arch, h->dev_block, archive, env_of_cell, n_cells, h->P.n_envs);
+  HIPCHK(h, hipGetLastError());
+  return SHIPSIM_OK;
+}
+
+int shipsim_archive_load(shipsim_handle* h, const void* archive, int64_t bytes, int32_t n_cells,
+                         const int32_t* cell_of_env) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  state_host::Table live, arch;
+  if (int rc = archive_call_check(h, "archive_load", archive, bytes, n_cells, cell_of_env, "cell_of_env", &live, &arch))
+    return rc;
+  DeviceGuard g(h->device);
+  shipsim_archive_gather_launch(h->stream, arch, live, archive, h->dev_block, cell_of_env, h->P.n_envs, n_cells);
+  HIPCHK(h, hipGetLastError());
+  h->ever_reset = 1;
   return SHIPSIM_OK;
 }
 

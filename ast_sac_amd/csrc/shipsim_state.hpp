@@ -136,3 +136,9 @@ void shipsim_c2_pipe_launch(int blocks, hipStream_t st, const Params& P, const D
 
 // level_distance_kernel over n_envs envs of n_ships ships (shipsim_resample.hip)
 void shipsim_level_distance_launch(hipStream_t st, const DevState& S, int n_envs, int n_ships, double* out);
+
+// archive_gather_kernel (shipsim_archive.hip): slot d of the n_dst slots of dst (laid out by dst_table) takes slot
+// index[d] of the n_src slots of src (src_table); an index outside [0, n_src) leaves slot d alone
+void shipsim_archive_gather_launch(hipStream_t st, const state_host::Table& src_table,
+                                   const state_host::Table& dst_table, const void* src, void* dst,
+                                   const int32_t* index, int32_t n_dst, int32_t n_src);

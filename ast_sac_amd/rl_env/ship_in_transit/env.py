@@ -162,6 +162,46 @@ class BatchedMultiShipRLEnv:
         self.fork(src, weather=weather)
         return src, w, total, status
 
+    # -- state archive (beyond the reference; shipsim.StateArchive) --
+    def archive(self, n_cells):
+        """A shipsim.StateArchive of n_cells cells: a store of env states of any size, of which update(cell, score,
+        carry) overwrites single cells with the best env seen and load(cell_of_env, carry) starts any env from any
+        cell — the cell store of Go-Explore, the node pool of a tree search. Weather stays with the slot, as under
+        fork(weather="keep"): an env loaded from a cell sails under the weather of the slot it lands in. The
+        caller's stream arrays (ep_idx, dec_idx, log_len, a policy counter, weights) go in `carry`."""
+        return self.sim.archive(n_cells)
+
+    def relative_cells(self, bins, radius):
+        """A Cartesian cell index per env, (n_envs,) int32 on the device, in [0, relative_cells_count(bins)): where
+        ship 1 lies relative to the own ship (ship 0) on a bins x bins grid over [-radius, radius) m in north and
+        east, the outermost bins taking everything beyond, by the env's sampling_count. In float64 on get_state's
+        values, in this order:
+            dn = north[1] - north[0];  de = east[1] - east[0];  inv = bins / (2.0 * radius)   (a host float)
+            bn = clamp(floor((dn + radius) * inv), 0, bins - 1);  be = the same of de
+            sc = clamp(sampling_count, 0, max_sampling_frequency)
+            cell = (sc * bins + bn) * bins + be;  -1 (no cell) where dn or de is NaN
+        Adds, multiplies and floor only, so numpy on the same values gives the same cell."""
+        bins, radius = int(bins), float(radius)
+        if bins < 1 or not radius > 0.0:
+            raise ValueError("relative_cells: bins >= 1 and radius > 0")
+        ns = self.sim.n_ships
+        if ns < 2:
+            raise ValueError("relative_cells: the env has no obstacle ship")
+        north = self.sim.get(abi.F_NORTH).view(self.n_envs, ns)
+        east = self.sim.get(abi.F_EAST).view(self.n_envs, ns)
+        dn, de = north[:, 1] - north[:, 0], east[:, 1] - east[:, 0]
+        inv = bins / (2.0 * radius)
+        bn = torch.floor((dn + radius) * inv).clamp(0, bins - 1)
+        be = torch.floor((de + radius) * inv).clamp(0, bins - 1)
+        sc = self.sim.get(abi.E_SAMPLING_COUNT).clamp(0, int(self.cfg.max_sampling_frequency)).to(torch.int64)
+        ok = (dn == dn) & (de == de)
+        cell = (sc * bins + torch.where(ok, bn, 0.0).to(torch.int64)) * bins + torch.where(ok, be, 0.0).to(torch.int64)
+        return torch.where(ok, cell, -1).to(torch.int32)
+
+    def relative_cells_count(self, bins):
+        """The number of cells relative_cells(bins, ...) indexes."""
+        return (int(self.cfg.max_sampling_frequency) + 1) * int(bins) * int(bins)
+
     # -- reference helpers (env.py:186-196) --
     def do_normalize_action(self, a_real):
         return 2.0 * (a_real - self.action_space.low) / (self.action_space.high - self.action_space.low) - 1.0

@@ -75,10 +75,16 @@ def load_library(path=LIB_PATH):
                            ("shipsim_fork", [P, P, C.c_int64, P]),
                            ("shipsim_resample_workspace_bytes", [C.c_int32]),
                            ("shipsim_resample", [C.c_int32, P, P, C.c_uint64, P, C.c_int32, P, C.c_int64, P, P, P, P, P]),
-                           ("shipsim_level_distance", [P, P])):
+                           ("shipsim_level_distance", [P, P]),
+                           ("shipsim_archive_bytes", [P, C.c_int32]),
+                           ("shipsim_archive_store", [P, P, C.c_int64, C.c_int32, P]),
+                           ("shipsim_archive_load", [P, P, C.c_int64, C.c_int32, P]),
+                           ("shipsim_archive_workspace_bytes", [C.c_int32]),
+                           ("shipsim_archive_elect", [C.c_int32, C.c_int32, P, P, P, P, P, C.c_int64, P, P, P])):
         try:
             getattr(L, name).argtypes = argtypes
-            if name in ("shipsim_state_bytes", "shipsim_resample_workspace_bytes"):
+            if name in ("shipsim_state_bytes", "shipsim_resample_workspace_bytes", "shipsim_archive_bytes",
+                        "shipsim_archive_workspace_bytes"):
                 getattr(L, name).restype = C.c_int64
         except AttributeError:
             if "SHIPSIM_LIB" not in os.environ:
@@ -102,7 +108,9 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_run_policy", "shipsim_diag_lane_faults", "shipsim_set_stream_tail", "shipsim_div_check",
                     "shipsim_sbmpc_eval_multi", "shipsim_set_weather", "shipsim_get_weather",
                     "shipsim_state_bytes", "shipsim_snapshot", "shipsim_restore", "shipsim_fork",
-                    "shipsim_resample_workspace_bytes", "shipsim_resample", "shipsim_level_distance")
+                    "shipsim_resample_workspace_bytes", "shipsim_resample", "shipsim_level_distance",
+                    "shipsim_archive_bytes", "shipsim_archive_store", "shipsim_archive_load",
+                    "shipsim_archive_workspace_bytes", "shipsim_archive_elect")
 
 
 class Snapshot:
@@ -117,6 +125,116 @@ class Snapshot:
 
     def clone(self):
         return Snapshot(self.data.clone(), self.kind, self.n_envs, self.n_ships, self.build)
+
+
+class StateArchive:
+    """A store of env states whose size is the caller's choice (ShipSim.archive): `data`, a zero-initialised uint8
+    device tensor holding the state block of n_cells envs (include/shipsim.h: shipsim_archive_store), with what an
+    archive keeps per cell beside it — `cell_score` (float64, NaN: the cell is empty), `cell_seen` (int32: the
+    candidates the cell has had) and `carry`, the per-cell copies of the caller's per-env tensors — and the shape it
+    belongs to: kind, n_ships and the build string of the library that laid it out. Any handle of that kind, ship
+    count and build, whatever its n_envs, may store into it and load from it (`sim`; default: the handle it was
+    made by). Weather is not state: it stays with the slot, as under fork(weather="keep"). Every method is
+    asynchronous on the current stream, without a host round trip or an allocation after the first call with the
+    same carry keys, and can be captured into a graph."""
+
+    def __init__(self, sim, n_cells):
+        n_cells = int(n_cells)
+        if not 1 <= n_cells <= abi.ARCHIVE_MAX_CELLS:
+            raise ShipSimError(f"archive: n_cells must be in 1..{abi.ARCHIVE_MAX_CELLS}, not {n_cells}")
+        self.sim, self.n_cells, self.device = sim, n_cells, sim.device
+        self.kind, self.n_ships, self.build = int(sim.cfg.kind), sim.n_ships, sim.L.shipsim_build_info().decode()
+        nbytes = int(sim.L.shipsim_archive_bytes(sim.h, n_cells))
+        if nbytes < 0:
+            raise ShipSimError(f"shipsim_archive_bytes failed ({nbytes})")
+        dev = self.device
+        self.data = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.cell_score = torch.full((n_cells,), float("nan"), dtype=torch.float64, device=dev)
+        self.cell_seen = torch.zeros(n_cells, dtype=torch.int32, device=dev)
+        self.workspace = torch.empty(int(sim.L.shipsim_archive_workspace_bytes(n_cells)), dtype=torch.uint8, device=dev)
+        self.env_of_cell = torch.full((n_cells,), -1, dtype=torch.int32, device=dev)
+        self.n_improved = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.carry = {}
+
+    def as_snapshot(self):
+        """The archive's bytes as a Snapshot of n_cells envs (they share the memory): what restore() and
+        fork(source=) of a handle of n_envs == n_cells take."""
+        return Snapshot(self.data, self.kind, self.n_cells, self.n_ships, self.build)
+
+    def _handle(self, sim, what):
+        sim = self.sim if sim is None else sim
+        mine = (self.kind, self.n_ships)
+        if (int(sim.cfg.kind), sim.n_ships) != mine:
+            raise ShipSimError(f"{what}: the archive is of (kind, n_ships) = {mine}, the handle of "
+                               f"{(int(sim.cfg.kind), sim.n_ships)}")
+        build = sim.L.shipsim_build_info().decode()
+        if self.build != build:
+            raise ShipSimError(f"{what}: the archive was laid out by another build ({self.build!r}, this is {build!r})")
+        if sim.device != self.device:
+            raise ShipSimError(f"{what}: the archive is on {self.device}, the handle on {sim.device}")
+        return sim
+
+    def _index(self, x, n, what):
+        t = torch.as_tensor(x, dtype=torch.int32, device=self.device).contiguous().reshape(-1)
+        if t.numel() != n:
+            raise ShipSimError(f"{what}: the index array has {t.numel()} entries, expected {n}")
+        return t
+
+    def store(self, env_of_cell, sim=None):
+        """Cell c takes the live state of env env_of_cell[c] (shipsim_archive_store); an index outside [0, n_envs)
+        leaves the cell as it is. Returns the index tensor used."""
+        sim = self._handle(sim, "archive store")
+        idx = self._index(env_of_cell, self.n_cells, "archive store")
+        sim._follow_stream()
+        sim._check(sim.L.shipsim_archive_store(sim.h, _ptr(self.data), self.data.numel(), self.n_cells, _ptr(idx)),
+                   "shipsim_archive_store")
+        self._keep = idx
+        return idx
+
+    def load(self, cell_of_env, carry=None, sim=None):
+        """Env i takes the state of cell cell_of_env[i] (shipsim_archive_load), and entry i of every tensor of
+        `carry` — a dict of per-env tensors under keys update() has carried — the cell's copy; an index outside
+        [0, n_cells) leaves env i and its entries alone. Returns the index tensor used."""
+        sim = self._handle(sim, "archive load")
+        idx = self._index(cell_of_env, sim.n_envs, "archive load")
+        for k in (carry or {}):
+            if k not in self.carry:
+                raise ShipSimError(f"archive load: no update() has carried {k!r}")
+        sim._follow_stream()
+        sim._check(sim.L.shipsim_archive_load(sim.h, _ptr(self.data), self.data.numel(), self.n_cells, _ptr(idx)),
+                   "shipsim_archive_load")
+        if carry:
+            ok = (idx >= 0) & (idx < self.n_cells)
+            at = idx.clamp(0, self.n_cells - 1).long()
+            for k, t in carry.items():
+                kept = self.carry[k][at]
+                t.copy_(torch.where(ok.view(-1, *([1] * (t.dim() - 1))), kept, t))
+        self._keep = idx
+        return idx
+
+    def update(self, cell, score, carry=None, sim=None):
+        """Elect, then store, in one call: per cell the best-scoring env among those cell[i] names (archive_elect:
+        NaN scores and cells outside [0, n_cells) do not take part, ties go to the lowest env index) takes the cell if
+        it is empty or strictly improved — its state (store), its score (cell_score) and its entries of `carry`, a
+        dict of per-env tensors (ep_idx, dec_idx, log_len, a policy counter, weights ...) of which the archive keeps a
+        per-cell copy under the same key. Returns (env_of_cell, n_improved): (n_cells,) and (1,) int32 device
+        tensors owned by the archive (the next update overwrites them), -1 where a cell stayed; nothing is copied to
+        the host."""
+        sim = self._handle(sim, "archive update")
+        archive_elect(cell, score, self.cell_score, self.cell_seen, workspace=self.workspace,
+                      out_env_of_cell=self.env_of_cell, out_n_improved=self.n_improved, n_envs=sim.n_envs)
+        self.store(self.env_of_cell, sim=sim)
+        if carry:
+            took = self.env_of_cell >= 0
+            at = self.env_of_cell.clamp(min=0).long()
+            for k, t in carry.items():
+                if t.shape[0] != sim.n_envs or t.device != self.device:
+                    raise ShipSimError(f"archive update: carry[{k!r}] must be a device tensor of {sim.n_envs} rows")
+                if k not in self.carry:
+                    self.carry[k] = torch.zeros((self.n_cells,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
+                kept = self.carry[k]
+                kept.copy_(torch.where(took.view(-1, *([1] * (t.dim() - 1))), t[at], kept))
+        return self.env_of_cell, self.n_improved
 
 
 def diag_lane_faults():
@@ -400,6 +518,11 @@ class ShipSim:
         self._check(self.L.shipsim_level_distance(self.h, _ptr(out)), "shipsim_level_distance")
         return out
 
+    def archive(self, n_cells):
+        """A StateArchive of n_cells cells for handles of this one's kind and ship count (include/shipsim.h:
+        shipsim_archive_store): zeroed, every cell empty. Allocates; call it outside graph capture."""
+        return StateArchive(self, n_cells)
+
     # -- per-env weather (include/shipsim.h: shipsim_set_weather) --
     WEATHER_KEYS = ("wind_speed", "wind_direction", "current_north", "current_east")
 
@@ -573,3 +696,49 @@ def resample(weight, potential, seed, counter, arrangement="in_place", out_src=N
     if rc:
         raise ShipSimError(f"shipsim_resample failed ({rc})")
     return src, wout, total, status
+
+
+ARCHIVE_MAX_CELLS = abi.ARCHIVE_MAX_CELLS
+_elect_ws = {}  # (device, n_cells) -> workspace: one per archive size, reused by every call that brings none
+
+
+def archive_elect(cell, score, cell_score, cell_seen=None, workspace=None, out_env_of_cell=None, out_n_improved=None,
+                  n_envs=None):
+    """Which env each cell of an archive takes (shipsim_archive_elect): env i is a candidate of cell cell[i] when that
+    index is in [0, n_cells) and score[i] is not NaN; a cell's winner is its candidate of the largest score (IEEE >,
+    ties to the lowest env index) and takes the cell when cell_score[c] is NaN (empty) or its score is strictly
+    greater. cell: (n_envs,) int32, score: (n_envs,) float64, cell_score: (n_cells,) float64, updated in place,
+    cell_seen: optional (n_cells,) int32, += the cell's candidates; all device tensors. Returns (env_of_cell int32
+    (n_cells,), -1 where the cell stays; n_improved int32 (1,)): env_of_cell is what StateArchive.store takes.
+    Asynchronous on the current stream and capturable; without `workspace` one is cached per (device, n_cells)."""
+    L = load_library()
+    cs = cell_score
+    if not isinstance(cs, torch.Tensor) or not cs.is_cuda or cs.dtype != torch.float64 or not cs.is_contiguous():
+        raise ShipSimError("archive_elect: cell_score must be a contiguous float64 device tensor")
+    dev, m = cs.device, int(cs.numel())
+    c = torch.as_tensor(cell, dtype=torch.int32, device=dev).contiguous().reshape(-1)
+    s = torch.as_tensor(score, dtype=torch.float64, device=dev).contiguous().reshape(-1)
+    n = int(c.numel())
+    if s.numel() != n or (n_envs is not None and n != int(n_envs)):
+        raise ShipSimError(f"archive_elect: {n} cells and {s.numel()} scores for {n if n_envs is None else n_envs} envs")
+    if not 1 <= m <= ARCHIVE_MAX_CELLS or not 1 <= n <= RESAMPLE_MAX_N:
+        raise ShipSimError(f"archive_elect: n_cells must be in 1..{ARCHIVE_MAX_CELLS} and n_envs in 1..{RESAMPLE_MAX_N}, "
+                           f"not {m} and {n}")
+    for name, t, k in (("cell_seen", cell_seen, m), ("out_env_of_cell", out_env_of_cell, m),
+                       ("out_n_improved", out_n_improved, 1)):
+        if t is not None and (t.dtype != torch.int32 or t.device != dev or not t.is_contiguous() or t.numel() != k):
+            raise ShipSimError(f"archive_elect: {name} must be a contiguous int32 tensor of {k} on {dev}")
+    if workspace is None:
+        key = (dev.index, m)
+        if key not in _elect_ws:
+            _elect_ws[key] = torch.empty(int(L.shipsim_archive_workspace_bytes(m)), dtype=torch.uint8, device=dev)
+        workspace = _elect_ws[key]
+    eoc = out_env_of_cell if out_env_of_cell is not None else torch.empty(m, dtype=torch.int32, device=dev)
+    k_out = out_n_improved if out_n_improved is not None else torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        rc = L.shipsim_archive_elect(n, m, _ptr(c), _ptr(s), _ptr(cs), _ptr(cell_seen), _ptr(workspace),
+                                     workspace.numel(), _ptr(eoc), _ptr(k_out), C.c_void_p(stream.cuda_stream))
+    if rc:
+        raise ShipSimError(f"shipsim_archive_elect failed ({rc})")
+    return eoc, k_out

@@ -97,6 +97,7 @@ TRAJ_ENV_COLS = 8
 TE_FLAG_COLLISION, TE_FLAG_IMMINENT = 1, 2
 SBMPC_IN = 17
 SBMPC_MULTI_IN = 10 + 7 * MAX_OBS  # shipsim_sbmpc_eval_multi rows (include/shipsim.h)
+ARCHIVE_MAX_CELLS = 1 << 22  # SHIPSIM_ARCHIVE_MAX_CELLS: the most cells of a state archive
 
 
 def events_to_string(bits):

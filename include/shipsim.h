@@ -399,6 +399,60 @@ int shipsim_resample(int32_t n, const double* weight, const double* potential, u
                      double* weight_out, double* total_out, int32_t* status_out, void* stream);
 int shipsim_level_distance(shipsim_handle* h, double* out);
 
+/* ---- state archive: elect per cell, store, start envs from it (additive to ABI 12) --------------------------
+ * An archive is a caller-owned device buffer, 16-byte aligned, that holds the state block of n_cells envs of the
+ * handle's ship count: the same 43 columns at the same bytes per env as the handle's own block, laid out for n_cells
+ * instead of n_envs (only the strides differ), shipsim_archive_bytes(h, n_cells) bytes (SHIPSIM_EINVAL for a NULL
+ * handle or n_cells outside 1..SHIPSIM_ARCHIVE_MAX_CELLS). Its size is the caller's choice, single cells of it are
+ * overwritten, and any env starts from any cell: the node pool of a tree search, the cell store of Go-Explore. An
+ * archive of n_cells == n_envs is byte for byte a snapshot, and shipsim_fork(h, archive, ...) takes it. The padding
+ * between the columns is never written: zero the buffer once if its bytes are to be compared.
+ *   shipsim_archive_store  cell c takes the live state of env env_of_cell[c] (n_cells int32 on the device). An index
+ *                          outside [0, n_envs) leaves cell c as it is. SHIPSIM_ESTATE before the first reset.
+ *   shipsim_archive_load   env i takes the state of cell cell_of_env[i] (n_envs int32 on the device), written
+ *                          straight into the live block: archive and block never overlap, so there is no staging
+ *                          block, and the block does not move (captured graphs stay valid). An index outside
+ *                          [0, n_cells) leaves env i alone. Marks the handle reset, as shipsim_restore does.
+ * Both are one kernel launch, asynchronous on the handle's stream, without allocation or synchronisation, and may
+ * be captured into a graph. The index is tested before any address is formed from it; the loads are gathered and
+ * the stores consecutive, so duplicate indices are harmless and no state can be torn. All kinds that shipsim_fork
+ * serves (AST with K = 1..4, NONIW, SINGLE); what is not state (weather, the config, the stream tail) stays with the
+ * slot, as under shipsim_fork, and the arrays the caller owns (ep_idx, dec_idx, log_len) are the caller's to keep
+ * per cell. SHIPSIM_EINVAL with the reason in shipsim_last_error: a NULL archive or index array; n_cells < 1 or
+ * above SHIPSIM_ARCHIVE_MAX_CELLS; bytes != shipsim_archive_bytes(h, n_cells); an archive not 16-byte aligned; a
+ * handle with trajectory recording enabled.
+ *
+ * shipsim_archive_elect decides which env each cell takes. It is stateless like shipsim_resample: no handle, device
+ * pointers, asynchronous on `stream`, no host synchronisation and no allocation, capturable; what its launches hand
+ * one another lives in `workspace`, a caller-owned device buffer of at least shipsim_archive_workspace_bytes(n_cells)
+ * bytes, 16-byte aligned (contents undefined before and after).
+ *   candidates  env i (of n_envs) is a candidate of cell cell[i] when that index is in [0, n_cells) and score[i] is
+ *               not NaN.
+ *   winner      of a cell: its candidate with the largest score by IEEE > (-0.0 and +0.0 compare equal); ties go to
+ *               the lowest env index.
+ *   fill        the winner takes the cell when cell_score[c] is NaN (the cell is empty) or its score is strictly
+ *               greater: env_of_cell_out[c] = the winner and cell_score[c] = its score as given. Otherwise
+ *               env_of_cell_out[c] = -1 and cell_score[c] stays. env_of_cell_out (n_cells int32) is what
+ *               shipsim_archive_store takes.
+ *   counts      cell_seen[c] (n_cells int32, may be NULL) += the cell's candidates; *n_improved_out (may be NULL) =
+ *               the number of cells taken.
+ * The result does not depend on the order in which anything runs: across envs it is a 64-bit unsigned max over an
+ * order-preserving image of the score, then a 32-bit min of the env index among the envs that hold the cell's max,
+ * and integer adds (ast_sac_amd/csrc/shipsim_archive_host.hpp; restated in tests/archive_ref.py). SHIPSIM_EINVAL,
+ * before any device call: n_envs < 1 or above 2^22; n_cells < 1 or above SHIPSIM_ARCHIVE_MAX_CELLS; a NULL cell,
+ * score, cell_score, workspace or env_of_cell_out; workspace_bytes too small or a workspace not 16-byte aligned.
+ * shipsim_archive_workspace_bytes gives SHIPSIM_EINVAL for such an n_cells and does not decrease with n_cells. */
+#define SHIPSIM_ARCHIVE_MAX_CELLS (1 << 22)
+int64_t shipsim_archive_bytes(const shipsim_handle* h, int32_t n_cells);
+int shipsim_archive_store(shipsim_handle* h, void* archive, int64_t bytes, int32_t n_cells,
+                          const int32_t* env_of_cell);
+int shipsim_archive_load(shipsim_handle* h, const void* archive, int64_t bytes, int32_t n_cells,
+                         const int32_t* cell_of_env);
+int64_t shipsim_archive_workspace_bytes(int32_t n_cells);
+int shipsim_archive_elect(int32_t n_envs, int32_t n_cells, const int32_t* cell, const double* score,
+                          double* cell_score, int32_t* cell_seen, void* workspace, int64_t workspace_bytes,
+                          int32_t* env_of_cell_out, int32_t* n_improved_out, void* stream);
+
 /* ---- trajectory recording (f1: simulation_results export) ----------------------------------
  * Per-tick rows of ShipModelAST/SimpleShipModel.store_simulation_data (ship_model.py:903-957,
  * run_colav/.../ship_model.py:418-444) for both ships, plus the RewardTracker entry of every tick
