@@ -15,7 +15,8 @@ SOURCES = {
                 "ast_sac_amd/csrc/shipsim_weather_host.hpp", "ast_sac_amd/csrc/shipsim_launch_host.hpp",
                 "ast_sac_amd/csrc/shipsim_state_host.hpp", "include/shipsim.h",
                 "ast_sac_amd/csrc/shipsim_resample.hip", "ast_sac_amd/csrc/shipsim_resample_host.hpp",
-                "ast_sac_amd/csrc/shipsim_archive.hip", "ast_sac_amd/csrc/shipsim_archive_host.hpp"],
+                "ast_sac_amd/csrc/shipsim_archive.hip", "ast_sac_amd/csrc/shipsim_archive_host.hpp",
+                "ast_sac_amd/csrc/shipsim_grouping_host.hpp"],
     "sacfused": ["ast_sac_amd/csrc/sac_kernels.hip", "include/sac_fused.h"],
 }
 

@@ -8,11 +8,16 @@
 //   -DSHIPSIM_ABL_*          ablations (scripts/build_ablations.sh; timing only, results intentionally differ):
 //                            NO_WIND, NO_MAPDIST, NO_GROUND, NO_SBLOOP, SB_NEVER, SB_NONE
 //   -DSHIPSIM_C2_ONE_WAVE    C2 simplified ticks on the one-wave single_tick_kernel (same results; timing A/B)
-//   -DSHIPSIM_SB_STATS       multi-obstacle SBMPC counters (requests, passes, lone passes, obstacle evaluations),
-//                            read back through shipsim_diag_lane_faults (words 16..31: eight u64)
+//   -DSHIPSIM_SB_STATS       SBMPC pass counters of the one- and the multi-obstacle optimiser (requests, passes, lone
+//                            passes; obstacle evaluations for K > 1), read back through shipsim_diag_lane_faults
+//                            (words 16..31: eight u64). Not together with SHIPSIM_LANECHECK: one read-out serves both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#if defined(SHIPSIM_LANECHECK) && defined(SHIPSIM_SB_STATS)
+#error "SHIPSIM_LANECHECK and SHIPSIM_SB_STATS share shipsim_diag_lane_faults' read-out (the statistics would read zeros): build one at a time"
+#endif
 
 namespace shipsim {
 namespace diag {

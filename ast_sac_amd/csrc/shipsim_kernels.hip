@@ -31,6 +31,7 @@
 #include "shipsim_config_host.hpp"   // shipsim_default_config and shipsim_create's host half
 #include "shipsim_launch_host.hpp"   // the list of step kernels and the choice among them
 #include "shipsim_weather_host.hpp"  // shipsim_set_weather's host half
+#include "shipsim_grouping_host.hpp" // shipsim_set_stream_grouping's host half
 #include "shipsim_state_host.hpp"    // the state block as a table of columns (snapshot / restore / fork)
 #include "shipsim_archive_host.hpp"  // shipsim_archive_store / _load's host half
 
@@ -785,6 +786,9 @@ struct StepArgs {
   ChainArgs CH;
   int32_t max_ticks;
   const double* weather;  // WX kernels: the handle's per-env weather array (kWeatherCols x n_envs), else unread
+  // decision streams: the env that slot (block * envs per wave + env row of the wave) runs, a permutation of
+  // 0 .. n_envs - 1 (shipsim_set_stream_grouping); NULL, and every other kernel: slot = env
+  const int32_t* slot_env;
 };
 typedef const __attribute__((address_space(4))) StepArgs* StepArgsPtr;
 __device__ __forceinline__ const StepArgs& step_args() {
@@ -909,7 +913,15 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // one wave per block: envs [blockIdx.x * epw, + epw) on lanes [0, epw * LPE); lanes past them idle
   const int epw = P.epw > 0 && P.epw <= 64 / LPE ? P.epw : 64 / LPE;  // (as step_blocks)
   const int eslot = (int)(threadIdx.x & 63) / LPE;
-  const int env = (int)blockIdx.x * epw + eslot;
+  int env = (int)blockIdx.x * epw + eslot;
+  // The decision streams run the env their slot is given (stream_order_kernel: envs of like episode phase share a
+  // wave, so their SBMPC requests fall on the same ticks and share passes). Nothing below knows the slot: state,
+  // route, table column, record ring, counters, weather and the policy's noise key all go through env / envc / qc,
+  // and an env's results do not depend on its wave-mates. A slot past n_envs stays invalid (slot_env is a
+  // permutation, so its entries are < n_envs).
+  if constexpr (CHAIN != 0) {
+    if (A0.slot_env != nullptr && eslot < epw && env < P.n_envs) env = A0.slot_env[env];
+  }
   const int lie = (int)(threadIdx.x & 63) % LPE;
   const int ship = lie % SLOTS;
   const int sub = lie / SLOTS;
@@ -1310,6 +1322,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       }
       double pb = 1.0, cb = 0.0;
       int need0 = 0;
+      diag::sb_stat_lanes(6, (need && sub == 0) ? 1u : 0u);  // (statistics builds: as the multi-obstacle branch)
+      diag::sb_stat_lanes(7, (going && is_test && sub == 0) ? 1u : 0u);
       // the optimiser's inputs, pass and hand-out only in a wave where some env requests it this tick (a
       // wave-uniform branch: every lane takes part in the exchanges inside)
       if (__any(need)) {
@@ -2182,6 +2196,54 @@ __global__ __launch_bounds__(256) void div_check_kernel(int n, const double* __r
   ref[i] = a / d;
 }
 
+// The decision streams' slot -> env order (shipsim_set_stream_grouping; host half: shipsim_grouping_host.hpp):
+// slot_env sorted by the envs' ticks since their last reset, ties by env index. Rank by counting: thread i counts the
+// envs that sort before env i, over tiles of kOrderThreads keys staged in LDS, and stores i at that slot — ranks of
+// a total order are a permutation, so every slot is written exactly once, without atomics and in bounded loops.
+// Every thread of a block takes part in the staging and its barriers; threads past n_envs store nothing.
+constexpr int kOrderThreads = 256;
+__device__ __forceinline__ int32_t stream_order_key(double time, double dt) {  // grouping_host::key_of
+  const double q = rint(time / dt);
+  if (!(q > 0.0)) return 0;
+  return q >= (double)grouping_host::kMaxKey ? grouping_host::kMaxKey : (int32_t)q;
+}
+__global__ __launch_bounds__(kOrderThreads) void stream_order_kernel(const double* __restrict__ time, int n_envs,
+                                                                     int n_ships, double dt,
+                                                                     int32_t* __restrict__ slot_env) {
+  __shared__ int32_t tile[kOrderThreads];
+  const int i = blockIdx.x * kOrderThreads + threadIdx.x;
+  const int32_t mine = i < n_envs ? stream_order_key(time[(size_t)i * n_ships], dt) : 0;  // (the test ship's clock)
+  int32_t rank = 0;
+  for (int base = 0; base < n_envs; base += kOrderThreads) {
+    const int j = base + (int)threadIdx.x;
+    // (a tile's slots past n_envs hold a key above every env's: never counted)
+    tile[threadIdx.x] = j < n_envs ? stream_order_key(time[(size_t)j * n_ships], dt) : INT32_MAX;
+    __syncthreads();
+    // the envs of an earlier tile have smaller indices than this block's, those of a later one larger: one
+    // comparison per env there, the index only within the block's own tile (block-uniform branches)
+    const int own = (int)blockIdx.x * kOrderThreads;
+    if (base < own) {
+#pragma unroll 8
+      for (int t = 0; t < kOrderThreads; ++t) rank += tile[t] <= mine ? 1 : 0;
+    } else if (base > own) {
+#pragma unroll 8
+      for (int t = 0; t < kOrderThreads; ++t) rank += tile[t] < mine ? 1 : 0;
+    } else {
+#pragma unroll 8
+      for (int t = 0; t < kOrderThreads; ++t) {
+        const int32_t k = tile[t];
+        rank += (k < mine || (k == mine && t < (int)threadIdx.x)) ? 1 : 0;
+      }
+    }
+    __syncthreads();
+  }
+  if (i < n_envs) slot_env[rank] = i;  // (rank < n_envs: it counts envs other than i)
+}
+__global__ __launch_bounds__(kOrderThreads) void stream_identity_kernel(int n_envs, int32_t* __restrict__ slot_env) {
+  const int i = blockIdx.x * kOrderThreads + threadIdx.x;
+  if (i < n_envs) slot_env[i] = i;
+}
+
 // shipsim_fork: env i of dst becomes env src_env[i] of src, for every column of the state block in one launch.
 // blockIdx.y is the column (state_host::table); a column of n_envs * env_bytes bytes is n_envs * (env_bytes / unit)
 // units, unit t of it lying at offset + t * unit, so consecutive lanes store consecutive units (consecutive envs for
@@ -2244,6 +2306,12 @@ struct shipsim_handle {
   // shipsim_fork from the live state gathers into this block of dev_bytes and copies it back (allocated at the
   // first such call)
   void* fork_block;
+  // shipsim_set_stream_grouping: the switch (grouping_host::default_on from create), the slot -> env permutation on
+  // the device (grouping_host::buffer_len entries, the identity from create; NULL: more envs than the handle
+  // groups), and whether it holds the identity now (what a launch with the switch off leaves behind)
+  int group_on;
+  int32_t* slot_env;
+  int slot_identity;
   char err[512];
 };
 
@@ -2372,6 +2440,23 @@ static int launch_ast(shipsim_handle* h, launch_host::Entry entry, const float* 
   a.obs_out = obs_out; a.reward_out = reward_out; a.done_out = done_out; a.events_out = events_out;
   a.ticks_out = ticks_out; a.ready_out = ready_out; a.CH = ch;
   a.weather = h->wx_on ? h->wx_dev : nullptr;
+  // the decision streams' slot -> env order, formed on the stream in front of the launch (no readback: the
+  // collector replays both in a graph); with the switch off the buffer goes back to the identity once and the
+  // kernel runs slot = env
+  if (entry != launch_host::kStep && h->slot_env) {
+    const int n = h->P.n_envs, ob = (n + kOrderThreads - 1) / kOrderThreads;
+    if (grouping_host::groups(entry, n, h->group_on != 0)) {
+      hipLaunchKernelGGL(stream_order_kernel, dim3(ob), dim3(kOrderThreads), 0, h->stream,
+                         (const double*)h->S.f(SF_TIME), n, (int)h->P.n_ships, h->P.dt, h->slot_env);
+      HIPCHK(h, hipGetLastError());
+      h->slot_identity = 0;
+      a.slot_env = h->slot_env;
+    } else if (!h->slot_identity) {
+      hipLaunchKernelGGL(stream_identity_kernel, dim3(ob), dim3(kOrderThreads), 0, h->stream, n, h->slot_env);
+      HIPCHK(h, hipGetLastError());
+      h->slot_identity = 1;
+    }
+  }
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
   return SHIPSIM_OK;
@@ -2479,6 +2564,17 @@ int shipsim_create(const shipsim_config* cfg_in, int32_t n_envs, int32_t n_obs_s
   hipLaunchKernelGGL(init_kernel, dim3(blocks), dim3(threads), 0, h->stream, h->P, h->S, h->K);
   e = hipGetLastError();
   if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "init_kernel: %s", hipGetErrorString(e));
+  // the decision streams' slot -> env permutation (AST handles of up to grouping_host::kMaxEnvs envs): the identity
+  h->group_on = grouping_host::default_on(cfg->collav, cfg->n_ships) ? 1 : 0;
+  if (const size_t len = cfg->kind == SHIPSIM_KIND_AST ? grouping_host::buffer_len(n_envs) : 0) {
+    e = hipMalloc(&h->slot_env, len * sizeof(int32_t));
+    if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "hipMalloc(stream order): %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(stream_identity_kernel, dim3((n_envs + kOrderThreads - 1) / kOrderThreads), dim3(kOrderThreads),
+                       0, h->stream, n_envs, h->slot_env);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, SHIPSIM_EHIP, "stream_identity_kernel: %s", hipGetErrorString(e));
+    h->slot_identity = 1;
+  }
   return SHIPSIM_OK;
 }
 
@@ -2495,6 +2591,7 @@ int shipsim_destroy(shipsim_handle* h) {
     if (h->tail_ctr) (void)hipFree(h->tail_ctr);
     if (h->wx_dev) (void)hipFree(h->wx_dev);
     if (h->fork_block) (void)hipFree(h->fork_block);
+    if (h->slot_env) (void)hipFree(h->slot_env);
   }
   free(h->wx_host);
   delete h;
@@ -2622,6 +2719,23 @@ int shipsim_set_stream_tail(shipsim_handle* h, int32_t extra_ticks) {
     HIPCHK(h, hipMalloc(&h->tail_ctr, sizeof(int32_t)));
   }
   h->tail_extra = extra_ticks;
+  return SHIPSIM_OK;
+}
+
+int shipsim_set_stream_grouping(shipsim_handle* h, int32_t on) {
+  if (!h) return SHIPSIM_EINVAL;
+  h->group_on = on != 0;
+  return SHIPSIM_OK;
+}
+
+int shipsim_get_stream_grouping(shipsim_handle* h, int32_t* slot_env_out) {
+  if (!h || !h->dev_block || !slot_env_out) return SHIPSIM_EINVAL;
+  if (!h->slot_env)
+    return fail(h, SHIPSIM_EINVAL, "get_stream_grouping: AST handles of up to %d envs hold a stream order",
+                (int)grouping_host::kMaxEnvs);
+  DeviceGuard g(h->device);
+  HIPCHK(h, hipMemcpyAsync(slot_env_out, h->slot_env, (size_t)h->P.n_envs * sizeof(int32_t), hipMemcpyDefault,
+                           h->stream));
   return SHIPSIM_OK;
 }
 

@@ -464,6 +464,7 @@ __device__ void sbmpc_cooperative(bool need, const SbIn& in, int n_samp, double 
   const int half = lane >> 5;
   const int scen = lane & 31;
   uint64_t req = __ballot(need);
+  diag::sb_stat_wave(0, req ? 1u : 0u);  // (the counters of sbmpc_cooperative_multi; nothing in the product build)
   while (req) {
     int src0 = __ffsll((unsigned long long)req) - 1;
     req &= req - 1;
@@ -472,6 +473,9 @@ __device__ void sbmpc_cooperative(bool need, const SbIn& in, int n_samp, double 
       src1 = __ffsll((unsigned long long)req) - 1;
       req &= req - 1;
     }
+    diag::sb_stat_wave(1, 1u);
+    diag::sb_stat_wave(2, src1 < 0 ? 1u : 0u);
+    diag::sb_stat_wave(3, src1 < 0 ? 1u : 2u);
     int src = half ? src1 : src0;
     int srcc = src < 0 ? src0 : src;
     SbIn g;

@@ -80,7 +80,9 @@ def load_library(path=LIB_PATH):
                            ("shipsim_archive_store", [P, P, C.c_int64, C.c_int32, P]),
                            ("shipsim_archive_load", [P, P, C.c_int64, C.c_int32, P]),
                            ("shipsim_archive_workspace_bytes", [C.c_int32]),
-                           ("shipsim_archive_elect", [C.c_int32, C.c_int32, P, P, P, P, P, C.c_int64, P, P, P])):
+                           ("shipsim_archive_elect", [C.c_int32, C.c_int32, P, P, P, P, P, C.c_int64, P, P, P]),
+                           ("shipsim_set_stream_grouping", [P, C.c_int32]),
+                           ("shipsim_get_stream_grouping", [P, P])):
         try:
             getattr(L, name).argtypes = argtypes
             if name in ("shipsim_state_bytes", "shipsim_resample_workspace_bytes", "shipsim_archive_bytes",
@@ -110,7 +112,8 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_state_bytes", "shipsim_snapshot", "shipsim_restore", "shipsim_fork",
                     "shipsim_resample_workspace_bytes", "shipsim_resample", "shipsim_level_distance",
                     "shipsim_archive_bytes", "shipsim_archive_store", "shipsim_archive_load",
-                    "shipsim_archive_workspace_bytes", "shipsim_archive_elect")
+                    "shipsim_archive_workspace_bytes", "shipsim_archive_elect", "shipsim_set_stream_grouping",
+                    "shipsim_get_stream_grouping")
 
 
 class Snapshot:
@@ -360,6 +363,21 @@ class ShipSim:
         (0: off). Per-env results are unchanged; only where launches end moves."""
         self._check(self.L.shipsim_set_stream_tail(self.h, int(extra_ticks)), "shipsim_set_stream_tail")
         self.stream_tail = int(extra_ticks)
+
+    def set_stream_grouping(self, on):
+        """Grouping of run_table / run_policy envs into waves by episode phase (shipsim_set_stream_grouping; from
+        create on for two-ship envs with collav sbmpc, off otherwise): each launch orders the envs by ticks since
+        their last reset, so wave-mates share SBMPC passes. Per-env results are unchanged, bit for bit."""
+        self._check(self.L.shipsim_set_stream_grouping(self.h, int(bool(on))), "shipsim_set_stream_grouping")
+        self.stream_grouping = bool(on)
+
+    def get_stream_grouping(self):
+        """(n_envs,) int32 device tensor: the env each slot of the last stream launch ran
+        (shipsim_get_stream_grouping); the identity before the first launch and after one with grouping off."""
+        t = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+        self._follow_stream()
+        self._check(self.L.shipsim_get_stream_grouping(self.h, _ptr(t)), "shipsim_get_stream_grouping")
+        return t
 
     def run_table(self, table, max_ticks, ep_idx, dec_idx, out=None, log=None, log_len=None):
         """Open-loop decision stream (shipsim_run_table): table (n_eps, n_dec, N) float32 scoping angles

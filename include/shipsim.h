@@ -591,6 +591,25 @@ int shipsim_run_policy(shipsim_handle* h, const float* policy, const float* w2t,
  * and for one obstacle ship per env (the K > 1 streams run as with 0). */
 int shipsim_set_stream_tail(shipsim_handle* h, int32_t extra_ticks);
 
+/* Grouping of the decision streams' envs into waves by episode phase (additive to ABI 12). The
+ * stream kernels run several envs per wave, and a wave's SBMPC pass stalls all of them while it serves at most two
+ * requests; envs whose episodes are out of phase request on different ticks and every pass serves one. In front of
+ * every shipsim_run_table / shipsim_run_policy launch a small kernel on the handle's stream therefore orders the
+ * envs by the ticks since their last reset (the test ship's clock over the time step; ties by env index) and the
+ * launch's slot s runs env slot_env[s], so wave-mates meet their obstacle on the same ticks again. Per-env results
+ * do not change, bit for bit: an env's records do not depend on its wave-mates. No host readback or
+ * synchronisation (graph-capturable). Handles of up to 65536 envs; larger ones run slot = env whatever the switch
+ * says, and shipsim_step and the recording kernels always do. shipsim_create leaves the switch on for two-ship envs
+ * with collav sbmpc (the headline stream: +2.7 %) and off otherwise: collav none / simple never run a pass, and the
+ * K > 1 streams have no launch tail to absorb the unlike amounts of work of waves of unlike phase (K = 2 measured
+ * slower with grouping, K = 4 faster).
+ *   shipsim_set_stream_grouping  on != 0: group; 0: slot = env, from the next launch on.
+ *   shipsim_get_stream_grouping  slot_env_out: n_envs int32 (host or device), the last stream launch's permutation
+ *                                (the identity before the first and after a launch with grouping off), copied on
+ *                                the handle's stream. SHIPSIM_EINVAL for a handle that holds none. */
+int shipsim_set_stream_grouping(shipsim_handle* h, int32_t on);
+int shipsim_get_stream_grouping(shipsim_handle* h, int32_t* slot_env_out);
+
 /* ---- per-env weather (ABI 12) ---------------------------------------------------------------
  * By default every env of a handle runs the config's weather (wind_speed, wind_direction,
  * current_velocity_component_from_north / _from_east). shipsim_set_weather gives every env its own: four HOST
