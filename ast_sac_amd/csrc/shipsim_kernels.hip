@@ -1236,7 +1236,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     bool sb_active = false;
     double sb_pb = 1.0, sb_cb = 0.0;  // (FLAT) the pass's result, handed out inside the going region
     if (COLLAV == SHIPSIM_COLLAV_SBMPC && SLOTS > 2) {  // do_list of every obstacle ship (env.py:366-370)
-      constexpr int NOB = SLOTS - 1 < SHIPSIM_MAX_OBS ? SLOTS - 1 : SHIPSIM_MAX_OBS;  // (slots past K duplicate a ship)
+      constexpr int NOB = launch_host::sbmpc_nob(SLOTS);  // (slots past K duplicate a ship)
       SbMulti<NOB> in;
       double obn[NOB], obe[NOB];
 #pragma unroll
@@ -2157,18 +2157,20 @@ __global__ __launch_bounds__(64) void sbmpc_eval_kernel(int n, double tf, double
 
 // SBMPC.get_optimal_ctrl_offset over a do_list of n_obs obstacles (sbmpc.py:113-185) for n independent requests
 // (shipsim_sbmpc_eval_multi): one request per lane, the optimisations served wave-cooperatively by the optimiser the
-// multi-obstacle env kernels run (sbmpc_cooperative_multi)
+// multi-obstacle env kernels run (sbmpc_cooperative_multi<NOB>), in the instantiations they run it in: the service
+// mirrors the env kernels of the same K (shipsim_sbmpc_eval_multi picks NOB), and reads NOB slots of a row
+template <int NOB>
 __global__ __launch_bounds__(64) void sbmpc_multi_eval_kernel(int n, int n_obs, int n_samp, double dt,
                                                               const double* __restrict__ in, double* __restrict__ out) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   const bool valid = i < n;
   const double* r = in + (size_t)(valid ? i : 0) * SHIPSIM_SBMPC_MULTI_IN;
-  SbMulti<SHIPSIM_MAX_OBS> q;
+  SbMulti<NOB> q;
   q.p_last = r[0]; q.chi_last = r[1]; q.u_d = r[2]; q.chi_d = r[3];
   q.os_x = r[4]; q.os_y = r[5]; q.os_v = r[8];  // os_state (x, y, psi, u, v, r): linear_pred uses x, y, v
   bool active = false;
 #pragma unroll
-  for (int k = 0; k < SHIPSIM_MAX_OBS; ++k) {
+  for (int k = 0; k < NOB; ++k) {
     const double* o = r + 10 + 7 * k;
     q.ob_x[k] = o[0]; q.ob_y[k] = o[1]; q.ob_psi[k] = o[2]; q.ob_u[k] = o[3]; q.ob_v[k] = o[4];
     q.obs_l[k] = o[5]; q.obs_w[k] = o[6];
@@ -2177,7 +2179,7 @@ __global__ __launch_bounds__(64) void sbmpc_multi_eval_kernel(int n, int n_obs, 
   }
   active = valid && active;
   double pb = 1.0, cb = 0.0;
-  sbmpc_cooperative_multi<SHIPSIM_MAX_OBS>(active, q, n_obs, n_samp, dt, pb, cb);  // (n_samp: int(tf / dt))
+  sbmpc_cooperative_multi<NOB>(active, q, n_obs, n_samp, dt, pb, cb);  // (n_samp: int(tf / dt))
   if (valid) {
     out[(size_t)i * 3 + 0] = active ? pb : 1.0;
     out[(size_t)i * 3 + 1] = active ? cb : 0.0;
@@ -3072,8 +3074,21 @@ int shipsim_sbmpc_eval_multi(int32_t n, int32_t n_obs, double tf, double dt, con
   if (n < 0 || n_obs < 1 || n_obs > SHIPSIM_MAX_OBS || (n > 0 && (!in || !out)) || !(dt > 0) || tf / dt > 4096)
     return SHIPSIM_EINVAL;
   if (n == 0) return SHIPSIM_OK;
-  hipLaunchKernelGGL(sbmpc_multi_eval_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, n_obs,
-                     (int)(tf / dt), dt, in, out);
+  // The service mirrors the env kernels of the same K: the optimiser instantiation (NOB) of the step kernel an env
+  // of 1 + n_obs ships runs, by the step kernels' own expressions (launch_host::ship_slots, sbmpc_nob). Those are
+  // the 4-slot kernels' (K = 2, 3) and the 8-slot kernels' (K = 4); K = 1, whose env kernels run the
+  // single-obstacle optimiser, is served by the 4-slot instantiation.
+  constexpr int kNob4 = launch_host::sbmpc_nob(4), kNob8 = launch_host::sbmpc_nob(8);
+  static_assert(kNob4 < kNob8 && kNob8 == SHIPSIM_MAX_OBS, "every n_obs <= SHIPSIM_MAX_OBS has an instantiation");
+  const bool wide = launch_host::sbmpc_nob(launch_host::ship_slots(1 + n_obs)) > kNob4;
+  const dim3 grid((n + 63) / 64), block(64);
+  const int n_samp = (int)(tf / dt);
+  if (wide)
+    hipLaunchKernelGGL(sbmpc_multi_eval_kernel<kNob8>, grid, block, 0, (hipStream_t)stream, n, n_obs, n_samp, dt, in,
+                       out);
+  else
+    hipLaunchKernelGGL(sbmpc_multi_eval_kernel<kNob4>, grid, block, 0, (hipStream_t)stream, n, n_obs, n_samp, dt, in,
+                       out);
   return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
 }
 

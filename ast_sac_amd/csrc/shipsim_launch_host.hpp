@@ -51,6 +51,13 @@ struct Selection {
   const char* why;  // NULL, or why no kernel serves this handle at this entry point (key, lpe, tail unset)
 };
 
+// ship slots per env: 2 for the two-ship envs, 4 or 8 with K > 1 obstacle ships (n_ships = 1 + K)
+constexpr int ship_slots(int n_ships) { return n_ships <= 2 ? 2 : (n_ships <= 4 ? 4 : 8); }
+
+// obstacles the SBMPC optimiser of a kernel with this many ship slots is built for (sbmpc_cooperative_multi<NOB>):
+// every slot but the ship under test's, at most SHIPSIM_MAX_OBS (slots past K duplicate a ship)
+constexpr int sbmpc_nob(int slots) { return slots - 1 < SHIPSIM_MAX_OBS ? slots - 1 : SHIPSIM_MAX_OBS; }
+
 // The kernel of a handle with this machinery, collav and ship count, whose uniform-weather lanes per env are
 // lpe_uniform (2, 4, 8 or 16: shipsim_create), with trajectory recording and per-env weather on or off, at an entry
 // point. Results are the same at every lanes-per-env, so where a family has no kernel at lpe_uniform the nearest
@@ -58,7 +65,7 @@ struct Selection {
 inline Selection select(int machinery, int collav, int n_ships, int lpe_uniform, bool recording, bool weather,
                         Entry entry) {
   const bool detailed = machinery == SHIPSIM_MACH_DETAILED;
-  const int slots = n_ships <= 2 ? 2 : (n_ships <= 4 ? 4 : 8);  // ship slots per env (K > 1 obstacle ships: 4 or 8)
+  const int slots = ship_slots(n_ships);
   if (slots > 2 && (!detailed || collav == SHIPSIM_COLLAV_SIMPLE))
     return {0, 0, false, "detailed machinery and collav none / sbmpc only"};
   if (weather && !detailed)

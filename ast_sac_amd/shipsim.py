@@ -658,7 +658,13 @@ def sbmpc_eval_multi(requests, n_obs, tf=1000.0, dt=20.0, device="cuda"):
     rc = L.shipsim_sbmpc_eval_multi(int(x.shape[0]), int(n_obs), float(tf), float(dt), _ptr(x), _ptr(out),
                                     C.c_void_p(stream.cuda_stream))
     if rc:
-        raise ShipSimError(f"shipsim_sbmpc_eval_multi failed ({rc}): n_obs must be 1..{abi.MAX_OBS}")
+        if rc != -1:  # (not SHIPSIM_EINVAL: SHIPSIM_EHIP)
+            why = "the launch failed"
+        elif not 1 <= int(n_obs) <= abi.MAX_OBS:
+            why = f"n_obs {int(n_obs)} must be 1..{abi.MAX_OBS}"
+        else:
+            why = f"bad argument (tf {float(tf)}, dt {float(dt)}: dt > 0 and tf / dt <= 4096)"
+        raise ShipSimError(f"shipsim_sbmpc_eval_multi failed ({rc}): {why}")
     return out
 
 

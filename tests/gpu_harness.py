@@ -139,6 +139,24 @@ def _compare_env(g_eps, o_eps, rtol):
     return worst, msgs
 
 
+def sensitive_envs(orcs, rtol=1e-5):
+    """The envs in which some oracle variant's records (run_oracle_variants) differ from variant 0's, by the
+    comparison a device result is held to (_compare_env): the envs the oracle itself shows to be ill-conditioned.
+    Outside this set the oracle's variants agree, and a device result must match the unperturbed oracle."""
+    return {i for i in range(len(orcs[0])) for orc in orcs[1:] if _compare_env(orc[i][0], orcs[0][i][0], rtol)[1]}
+
+
+def check_sensitive(chosen, orcs, max_share=0.25):
+    """The input condition and the per-env statement of the oracle-variant tests: at most max_share of the envs are
+    sensitive (so the rest are pinned to the exact oracle), and every env matched only by a perturbed variant is
+    one of them. Returns the sensitive set."""
+    S = sensitive_envs(orcs)
+    assert len(S) / len(chosen) <= max_share, (len(S), len(chosen))
+    outside = sorted(set(np.nonzero(np.asarray(chosen) != 0)[0].tolist()) - S)
+    assert not outside, f"envs off the unperturbed oracle although the oracle's variants agree: {outside[:20]}"
+    return S
+
+
 def compare(gpu_rec, orcs, rtol=1e-5):
     """gpu_rec vs a list of oracle variants (run_oracle_variants; a bare run_oracle result is
     accepted too). Returns (worst error over envs, mismatch messages, per-env chosen variant)."""

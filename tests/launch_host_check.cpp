@@ -115,6 +115,11 @@ int main() {
       CHECK(!s.why && s.lpe == 16 && !s.tail);
       CHECK(s.key == L::step_key(true, SB, 16, false, 1 | (wx ? 4 : 0), n_ships <= 4 ? 4 : 8));
     }
+  // the SBMPC optimiser a K-obstacle env's kernel is built for (and shipsim_sbmpc_eval_multi mirrors): three
+  // obstacles in the 4-slot kernels (K = 2, 3), four in the 8-slot ones (K = 4)
+  static_assert(L::ship_slots(2) == 2 && L::ship_slots(3) == 4 && L::ship_slots(4) == 4 && L::ship_slots(5) == 8, "");
+  static_assert(L::sbmpc_nob(L::ship_slots(1 + 2)) == 3 && L::sbmpc_nob(L::ship_slots(1 + 3)) == 3, "");
+  static_assert(L::sbmpc_nob(L::ship_slots(1 + 4)) == 4 && L::sbmpc_nob(8) == SHIPSIM_MAX_OBS, "");
   CHECK(L::select(S, SB, 3, 16, false, false, L::kStep).why != nullptr);
   CHECK(L::select(D, SHIPSIM_COLLAV_SIMPLE, 5, 16, false, false, L::kPolicy).why != nullptr);
   CHECK(L::select(D, SB, 2, 16, true, false, L::kTable).why != nullptr);

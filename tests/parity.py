@@ -6,9 +6,36 @@ crossing zero — rudder angle, sway speed, yaw rate — are judged on the colum
 Integer / event quantities (tick counts, event bits, done flags, waypoint indices) must match
 exactly.
 """
+import json
+import os
+import time
+
 import numpy as np
 
 RTOL = 1e-5
+
+
+def record(row):
+    """One parity row of a GPU test (case, envs checked, decisions checked, sensitive, perturbed, off-oracle, worst
+    rel err, explained sbmpc mismatches; None where a case has no such figure), stamped with the time and the
+    library's build: appended as one JSON line to $SHIPSIM_PARITY_LOG when that is set, printed otherwise."""
+    row = dict(row, time=time.strftime("%Y-%m-%dT%H:%M:%S"),
+               library=__import__("ast_sac_amd.shipsim", fromlist=["x"]).load_library().shipsim_build_info().decode())
+    line = json.dumps(row)
+    path = os.environ.get("SHIPSIM_PARITY_LOG")
+    if not path:
+        print("\n[parity] " + line)
+        return
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "a") as f:
+        f.write(line + "\n")
+
+
+def parity_row(case, envs_checked=None, decisions_checked=None, sensitive=None, perturbed=None, off_oracle=None,
+               worst_rel_err=None, sbmpc_explained=None, **more):
+    return dict(case=case, envs_checked=envs_checked, decisions_checked=decisions_checked, sensitive=sensitive,
+                perturbed=perturbed, off_oracle=off_oracle, worst_rel_err=worst_rel_err,
+                sbmpc_explained=sbmpc_explained, **more)
 
 
 def rel_err(got, ref, floor_frac=0.01):

@@ -4,7 +4,7 @@ import pytest
 
 import gpu_harness as H
 from ast_sac_amd import shipsim_abi as abi
-from parity import assert_close, rel_err
+from parity import assert_close, parity_row, record, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -120,6 +120,10 @@ def test_ast_env_vs_oracle(torch_cuda, collav, machinery, n_envs, n_eps):
     assert worst <= 1e-5
     # ill-conditioned envs (matched only by a perturbed oracle run) must stay rare
     assert (chosen != 0).mean() <= 0.1, (chosen != 0).sum()
+    S = H.check_sensitive(chosen, orcs)  # a perturbed match only where the oracle's own variants disagree
+    record(parity_row(f"ast_env_vs_oracle[{collav}-{machinery}-{n_envs}-{n_eps}]", envs_checked=n_envs,
+                      decisions_checked=sum(len(d) for env in gpu for (_, d) in env), sensitive=len(S),
+                      perturbed=int((chosen != 0).sum()), off_oracle=0, worst_rel_err=worst))
     orc = [orcs[v][i] for i, v in enumerate(chosen)]
     # end-of-run ship state, both ships of every env
     ships = np.array([o[1] for o in orc])  # (N, 2, 20)

@@ -33,7 +33,7 @@ def _far_traffic(cfg, k_total):
 
 
 @pytest.mark.parametrize("collav", ["none", "sbmpc"])
-@pytest.mark.parametrize("k", [2, 4])
+@pytest.mark.parametrize("k", [2, 3, 4])
 def test_far_traffic_reduces_to_one_obstacle(collav, k):
     tables = H.make_tables(6, 2, seed=77)
     ref = H.run_oracle(abi.ast_config(collav), tables)
@@ -70,3 +70,72 @@ def test_multi_obstacle_episodes_run(collav, k):
             assert ships[s][7] > 0
             init = cfg.ship[s]
             assert (ships[s][0], ships[s][1]) != (init.initial_north_position_m, init.initial_east_position_m)
+
+
+def test_third_obstacle_comes_within_reach_at_k3():
+    """Coverage of the K = 3 sbmpc tables of tests/test_gpu_multi_obstacle.py::test_multi_obstacle_vs_oracle (seed 11,
+    two episodes): on some ticks the third obstacle ship is within SBMPC's D_INIT (2000 m) of the ship under test,
+    so the optimiser's second obstacle pair (obstacle 2 alone, csrc/shipsim_sbmpc.hpp) evaluates a real scenario
+    cost there and not only the out-of-reach constant. Measured over the first 16 envs' two episodes: 2,352 of
+    35,792 ticks (about 1,200 of 18,000 per episode). The default traffic never has three obstacles in range at once (0 ticks, measured at K = 3 and K = 4,
+    asserted for K = 3 here), so the env tests never run a scenario cost for all of a do_list of three; the service
+    tests (tests/test_gpu_sbmpc_multi.py) are what cover that."""
+    cfg = abi.ast_config("sbmpc", n_obs_ships=3)
+    tables = H.make_tables(64, 2, seed=11, special=False)[:16]
+    near3 = all3 = total = 0
+    for eps in tables:
+        env = O.OracleEnv(cfg, log_cap=8000)
+        for table in eps:
+            env.reset()  # (the row sinks start again with the episode)
+            for a_norm in table:
+                if env.step(abi.normalized_to_scoping(a_norm))[2]:
+                    break
+            rows = [env.raw_rows(s) for s in range(4)]  # one row per ship per tick (a stopped ship repeats its last)
+            n = len(rows[0])
+            assert all(len(r) == n for r in rows) and 0 < n < 8000
+            own = rows[0][:, 1:3]  # SHIPSIM_TS_NORTH, SHIPSIM_TS_EAST
+            dist = [np.hypot(*(rows[s][:, 1:3] - own).T) for s in (1, 2, 3)]
+            near3 += int((dist[2] < 2000.0).sum())
+            all3 += int(((dist[0] < 2000.0) & (dist[1] < 2000.0) & (dist[2] < 2000.0)).sum())
+            total += n
+    print(f"\nthird obstacle within D_INIT on {near3} of {total} ticks; all three on {all3}")
+    assert total > 10000
+    assert near3 >= 100
+    assert all3 == 0
+
+
+def _rec(obs, reward=1.0, done=False, bits=0, ticks=100):
+    return (np.asarray(obs, np.float32), reward, done, bits, ticks)
+
+
+def test_sensitive_envs_on_hand_made_records():
+    """gpu_harness.sensitive_envs / check_sensitive: an env is sensitive when some variant's records differ from
+    variant 0's in anything a device result is held to (tick count, event bits, done, obs or reward beyond 1e-5,
+    the number of decisions or episodes), and not for a difference inside the tolerance or in bits the comparison
+    masks; a perturbed match outside the set fails."""
+    o = np.arange(1.0, 9.0)
+    base = ([(o, [_rec(o), _rec(2 * o)])], None, None)
+
+    def variant(**kw):
+        return ([(o, [_rec(o), _rec(2 * o, **kw)])], None, None)
+
+    envs0 = [base] * 8
+    envs1 = [base,                                             # 0: identical
+             variant(ticks=101),                               # 1: tick count
+             variant(bits=1 << 5),                             # 2: event bits
+             variant(done=True),                               # 3: done
+             variant(reward=1.0 + 1e-3),                       # 4: reward
+             ([(o, [_rec(o)])], None, None),                   # 5: fewer decisions
+             variant(reward=1.0 + 1e-9),                       # 6: inside the tolerance
+             variant(bits=1 << 24)]                            # 7: a bit the comparison masks
+    envs2 = list(envs0)
+    envs2[0] = ([(o, [_rec(o), _rec(2 * o * (1 + 1e-3))])], None, None)  # 0: obs, in the third variant only
+    assert H.sensitive_envs([envs0, envs0]) == set()
+    assert H.sensitive_envs([envs0, envs1]) == {1, 2, 3, 4, 5}
+    assert H.sensitive_envs([envs0, envs1, envs2]) == {0, 1, 2, 3, 4, 5}
+    orcs = [envs0, envs1]
+    assert H.check_sensitive(np.array([0, 1, 0, 0, 0, 0, 0, 0]), orcs, max_share=1.0) == {1, 2, 3, 4, 5}
+    with pytest.raises(AssertionError, match="variants agree"):
+        H.check_sensitive(np.array([0, 0, 0, 0, 0, 0, 1, 0]), orcs, max_share=1.0)
+    with pytest.raises(AssertionError):
+        H.check_sensitive(np.zeros(8, int), orcs)  # 5 of 8 sensitive: over a quarter, the inputs pin too little
