@@ -221,6 +221,30 @@ __device__ __forceinline__ void sincos2(double a, double b, bool odd, double& sa
   }
 }
 
+// sqrt of two values of a ship in one call: its even sub-lanes evaluate a, its odd ones b (`odd` = odd sub-lane),
+// and the pairs exchange the results (the ship's lane parity is kept: quad_perm [2,3,0,1]). Every sub-lane of the
+// ship must be active and hold the same a and b; the values are those of two separate calls.
+__device__ __forceinline__ void sqrt2(double a, double b, bool odd, double& ra, double& rb) {
+  const double r = sqrt(odd ? b : a);
+  const double o = sub_pair_swap(r);
+  ra = odd ? o : r;
+  rb = odd ? r : o;
+}
+// sqrt of three values of a two-ship env row in one call. `a` is per ship (each ship's own), `b` is the first
+// ship's only (is_first: this lane is one of its), `c` the second ship's only: even sub-lanes evaluate a, odd ones
+// b / c, the pairs exchange, and the odd value crosses to the other ship's lane of the same sub-lane (pair_swap).
+// ra = sqrt(a); rb = sqrt(b) on both ships' lanes; rc = sqrt(c) on the first ship's lanes (its partner's), 0 on the
+// second's own. The whole row must be active.
+__device__ __forceinline__ void sqrt3_row(double a, double b, double c, bool odd, bool is_first, double& ra,
+                                          double& rb, double& rc) {
+  const double mine = is_first ? b : c;
+  double second;
+  sqrt2(a, mine, odd, ra, second);
+  const double other = pair_swap(second);  // first ship's lanes: sqrt(c); second ship's: sqrt(b)
+  rb = is_first ? second : other;
+  rc = is_first ? other : 0.0;
+}
+
 // get_wind_force :497-517 (sw, cw = sin/cos(wind_direction - yaw))
 template <bool PAIRED>
 __device__ __forceinline__ void wind_force(const ShipConst& c, const Params& P, const Ship& s, double sw, double cw,

@@ -867,6 +867,20 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // row, so inside one `if (going)` a source lane is active exactly when its destination is. (The SBMPC pass itself
   // is wave-cooperative across envs and stays outside the region.)
   static_assert(!FLAT || (LPE == 16 && SLOTS == 2), "the flat tick: env = one DPP row, going per env");
+  // The same streams shorten the tick's serial stream over the ship's idle sub-lanes and by dropping branches whose
+  // two sides are pure (DESIGN.md §9 "Roots over sub-lanes, pure branches"). LM_POST: the three square roots after
+  // the Euler step (each ship's ground distance, the reward's distance, the obstacle ship's travel step) in one call
+  // over the env row, one argument per sub-lane parity and ship, exchanged by DPP (sqrt3_row, shipsim_device.hpp);
+  // the call sits inside the flat `going` region and outside every per-ship guard, where the whole row is active.
+  // LM_OUT: the map bounds test without short-circuit branches. LM_REQ: the test ship's request block in front of
+  // the SBMPC pass on every lane, the obstacle ship's lanes keeping their state by selects. (SHIPSIM_LANE_MATH: a
+  // bit per step, for the narrowed timing variants of scripts/build_variant.sh; the product has all three.)
+#ifndef SHIPSIM_LANE_MATH
+#define SHIPSIM_LANE_MATH 7
+#endif
+  constexpr bool LM_POST = FLAT && (SHIPSIM_LANE_MATH & 1);
+  constexpr bool LM_OUT = FLAT && (SHIPSIM_LANE_MATH & 2);
+  constexpr bool LM_REQ = FLAT && (SHIPSIM_LANE_MATH & 4);
   using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
   // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
   // instantiation compiles to the code it had (the dead arm of a constant condition is not emitted)
@@ -1296,6 +1310,18 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       if constexpr (FLAT) {  // the flat tick: the two guards below as one
         if (going) {
           los_pre_q = los_q(c, s, s.n, s.e, los_pre_e);
+          if constexpr (LM_REQ) {
+            // the block below on every lane, without the role guard: its updates are pure, and the obstacle ship's
+            // lanes keep their state by selects (their los_arg and need are not read)
+            const double ect0 = s.e_ct, eint0 = s.e_ct_int;
+            s.e_ct = los_pre_e;
+            los_arg = los_windup(c, s, los_pre_q);
+            s.e_ct = is_test ? s.e_ct : ect0;
+            s.e_ct_int = is_test ? s.e_ct_int : eint0;
+            double d0 = pe - s.e, d1 = pn - s.n;
+            need = (int)is_test & (int)sqrt_lt(d0 * d0 + d1 * d1, 2000.0);  // D_INIT_
+            need = diag::sb_request(need, PT.max_sampling);
+          } else
           if (is_test) {
             s.e_ct = los_pre_e;
             los_arg = los_windup(c, s, los_pre_q);
@@ -1368,6 +1394,7 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     }
     // ---- ship ticks (test_step :345-445 / obs_step :447-536) ----
     double my_speed_out = 0.0, dtravel = 0.0, dtime = 0.0;
+    double dtravel2 = 0.0;  // (LM_POST) the obstacle ship's squared travel step; 0 where it has none (frozen)
     double ep_n = 0.0, ep_e = 0.0, ep_dt = 0.0;  // (EARLY_MAP) the position after this tick's step, and the step
     if (FLAT || going) {
       if constexpr (EARLY_MAP) {
@@ -1420,7 +1447,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         my_speed_out = U;
         if (is_obs1) {  // travel tracker (env.py:527-534, Q6)
           double tn = s.log_n - prev_log_n, te = s.log_e - prev_log_e;
-          dtravel = sqrt(tn * tn + te * te);
+          if constexpr (LM_POST) dtravel2 = tn * tn + te * te;  // (its root: with the ground distance's, below)
+          else dtravel = sqrt(tn * tn + te * te);
           dtime = PT.dt;
         }
       }
@@ -1487,12 +1515,27 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     }
     int gri = gr ? XF_GROUND : 0;
     ship_or<LPE, SLOTS>(gri);
-    const double my_ground = sqrt(d2);
+    double my_ground, lm_on = 0.0, lm_oe = 0.0, lm_dist = 0.0, lm_odtravel = 0.0;
+    if constexpr (LM_POST) {
+      // the three roots after the step in one call: each ship's ground distance on its even sub-lanes; on the odd
+      // ones the reward's distance (the test ship's lanes: the same bits from either ship, (-x)² = x²) and the
+      // obstacle ship's travel step (its own lanes; 0 when frozen, whose root is the 0 the guarded tick adds)
+      SHIPSIM_LANE_CHECK(LPE, 13);
+      lm_on = pair_swap(s.n); lm_oe = pair_swap(s.e);
+      const double dx = lm_on - s.n, dy = lm_oe - s.e;
+      sqrt3_row(d2, dx * dx + dy * dy, dtravel2, sub & 1, is_test, my_ground, lm_dist, lm_odtravel);
+    } else {
+      my_ground = sqrt(d2);
+    }
     PT_MARK(2);
     bool my_end = false, my_outside = false, my_roa = false, my_nf = false;
     if (FLAT || going) {
       my_end = sqrt_le((s.n - s.end_n) * (s.n - s.end_n) + (s.e - s.end_e) * (s.e - s.end_e), 200.0);
       double margin = c.l_ship / 2;
+      if constexpr (LM_OUT)  // (the four comparisons are pure: no short-circuit branches)
+        my_outside = ((int)(s.n < PT.min_north + margin) | (int)(s.n > PT.max_north - margin) |
+                      (int)(s.e < PT.min_east + margin) | (int)(s.e > PT.max_east - margin)) != 0;
+      else
       my_outside = (s.n < PT.min_north + margin || s.n > PT.max_north - margin) ||
                    (s.e < PT.min_east + margin || s.e > PT.max_east - margin);
       double rdn = s.n - s.wp_n, rde = s.e - s.wp_e;  // is_reach_radius_of_acceptance (obstacle ship)
@@ -1515,9 +1558,14 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       Tn = s.n; Te = s.e; Th = s.yaw; Tsh = sy; Tch = cy; Tect = s.log_ect; Tground = my_ground; Ttime = s.time;
       Tf = my_flags;
       Of = pair_swap_i(my_flags);
-      On = pair_swap(s.n); Oe = pair_swap(s.e); Oyaw = pair_swap(s.yaw);
+      if constexpr (LM_POST) { On = lm_on; Oe = lm_oe; }  // (exchanged in front of the batched roots)
+      else { On = pair_swap(s.n); Oe = pair_swap(s.e); }
+      Oyaw = pair_swap(s.yaw);
       Oect = pair_swap(s.log_ect); Oground = pair_swap(my_ground);
-      Ospeed = pair_swap(my_speed_out); Odtravel = pair_swap(dtravel); Odtime = pair_swap(dtime);
+      Ospeed = pair_swap(my_speed_out);
+      if constexpr (LM_POST) Odtravel = lm_odtravel;  // (sqrt3_row: the partner's root, crossed already)
+      else Odtravel = pair_swap(dtravel);
+      Odtime = pair_swap(dtime);
       Cn = On; Ce = Oe;
       any_nf = (my_flags | Of) & XF_NONFINITE;
     } else {  // slot k's first lane of the env row holds ship k
@@ -1558,7 +1606,9 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
       const bool is_tnav = fabs(Tect) > 3000;
       const bool is_onav = (travel_dist > PT.AB_seg * 2) || (travel_time > INFINITY) || (fabs(Oect) > 500);
       double dx = Cn - Tn, dy = Ce - Te;
-      double dist = sqrt(dx * dx + dy * dy);
+      double dist;
+      if constexpr (LM_POST) dist = lm_dist;
+      else dist = sqrt(dx * dx + dy * dy);
       const bool enc_ok = !overtaking_sector(dx, dy, dist, Tsh, Tch, Th);  // head-on or crossing (Q5)
       // the five shaped terms of reward_designs.py:33-55 (RewardDesign4 / 3): one exp each,
       // evaluated by five lanes of the env in one call when LPE >= 8, then gathered
