@@ -16,7 +16,7 @@ SOURCES = {
                 "ast_sac_amd/csrc/shipsim_state_host.hpp", "include/shipsim.h",
                 "ast_sac_amd/csrc/shipsim_resample.hip", "ast_sac_amd/csrc/shipsim_resample_host.hpp",
                 "ast_sac_amd/csrc/shipsim_archive.hip", "ast_sac_amd/csrc/shipsim_archive_host.hpp",
-                "ast_sac_amd/csrc/shipsim_grouping_host.hpp"],
+                "ast_sac_amd/csrc/shipsim_grouping_host.hpp", "ast_sac_amd/csrc/shipsim_sbmpc_nominal.hpp"],
     "sacfused": ["ast_sac_amd/csrc/sac_kernels.hip", "include/sac_fused.h"],
 }
 

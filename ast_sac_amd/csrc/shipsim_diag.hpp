@@ -67,9 +67,12 @@ __device__ __forceinline__ bool sb_request(bool need, int max_sampling) {
 // ---- multi-obstacle SBMPC counters (SHIPSIM_SB_STATS) -----------------------------------------------------------
 // [0] wave-ticks whose optimiser ran a pass, [1] passes, [2] lone-request passes, [3] requests served, [4] obstacle
 // evaluations (scenario lanes with a horizon), [5] far-skipped obstacle evaluations (scenario lanes), [6] env-ticks
-// with a request, [7] env-ticks (the test ship's sub-lane 0 ticking)
+// with a request, [7] env-ticks (the test ship's sub-lane 0 ticking), [8] requests the nominal-scenario test answered
+// without a pass (sbmpc_nominal_holds; the headline streams), [9] wave-ticks with a request whose requests it all
+// answered (no pass at all)
 #ifdef SHIPSIM_SB_STATS
-__device__ unsigned long long g_sb_stats[8];
+constexpr int kSbStats = 10;
+__device__ unsigned long long g_sb_stats[kSbStats];
 // v summed over the wave's active lanes, one atomic per wave
 __device__ __forceinline__ void sb_stat_lanes(int k, unsigned v) {
   const uint64_t ex = __builtin_amdgcn_read_exec();

@@ -37,6 +37,13 @@
 
 #include "shipsim_diag.hpp"  // diagnostics / ablation hooks (none in the product build)
 
+// Steps of the headline sbmpc streams' pass-free SBMPC answer (ast_step_kernel: SB_NOM, SB_NOM_ALG), a bit per step
+// for the narrowed timing variants of scripts/build_variant.sh: 1 the test, 2 its course terms without the atan;
+// 0 is the tick without the test. The product has both.
+#ifndef SHIPSIM_SB_NOMINAL
+#define SHIPSIM_SB_NOMINAL 3
+#endif
+
 using namespace shipsim;
 static_assert(kWeatherCols == weather_host::kCols && WX_WIND_SPEED == weather_host::kWindSpeed &&
                   WX_WIND_SIN == weather_host::kWindSin && WX_WIND_COS == weather_host::kWindCos &&
@@ -881,6 +888,15 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   constexpr bool LM_POST = FLAT && (SHIPSIM_LANE_MATH & 1);
   constexpr bool LM_OUT = FLAT && (SHIPSIM_LANE_MATH & 2);
   constexpr bool LM_REQ = FLAT && (SHIPSIM_LANE_MATH & 4);
+  // The same streams with collav sbmpc answer a request whose nominal scenario provably wins (sbmpc_nominal_holds,
+  // shipsim_sbmpc_nominal.hpp: memory at rest and the closest approach far enough that the nominal scenario's
+  // collision cost stays below every other scenario's own terms) on the requesting env's own lanes: the pass would
+  // return (1.0, +0.0) bit for bit, and runs only for the requests left (DESIGN.md §9 "The nominal scenario wins").
+  // SB_NOM_ALG: sin / cos of the desired course from the segment's and 1 / sqrt(1 + los_arg²); the atan is left to
+  // the requests that go to the pass (sbmpc_nominal_holds_seg). (SHIPSIM_SB_NOMINAL, at the top of the file: a bit per
+  // step.)
+  constexpr bool SB_NOM = LM_REQ && COLLAV == SHIPSIM_COLLAV_SBMPC && (SHIPSIM_SB_NOMINAL & 1);
+  constexpr bool SB_NOM_ALG = SB_NOM && (SHIPSIM_SB_NOMINAL & 2);
   using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
   // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
   // instantiation compiles to the code it had (the dead arm of a constant condition is not emitted)
@@ -1359,12 +1375,32 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         in.u_d = SC[0].desired_speed;  // the same in every lane (sbmpc_cooperative<true>)
         in.obs_l = SC[1].obs_l_cfg; in.obs_w = SC[1].obs_w_cfg;
         if (going && is_test) {
-          if (need) in.chi_d = -(s.seg_alpha + atan(los_arg));
+          if constexpr (!SB_NOM_ALG) {
+            if (need) in.chi_d = -(s.seg_alpha + atan(los_arg));
+          }
           in.os_x = s.e; in.os_y = s.n; in.os_v = s.v;
           in.ob_x = pe; in.ob_y = pn; in.ob_psi = -pyaw; in.ob_u = pu; in.ob_v = pv;
           in.ob_so = -psy; in.ob_co = pcy;  // sin(-yaw) = -sin(yaw), cos(-yaw) = cos(yaw)
           in.p_last = p_last; in.chi_last = chi_last;
         }
+        if constexpr (SB_NOM) {
+          // every request of the wave tested at once, on all lanes (a ship's sub-lanes redundantly, like the rest of
+          // the chain; the obstacle ship's lanes on zeros, their result masked by need)
+          bool fast;
+          if constexpr (SB_NOM_ALG) {
+            fast = need & sbmpc_nominal_holds_seg(in, s.seg_sin, s.seg_cos, los_arg, PT.sbmpc_nsamp, PT.sbmpc_dt).holds;
+            if (need & !fast) in.chi_d = -(s.seg_alpha + atan(los_arg));
+          } else {
+            fast = need & sbmpc_nominal_holds(in, PT.sbmpc_nsamp, PT.sbmpc_dt).holds;
+          }
+          diag::sb_stat_lanes(8, (fast && sub == 0) ? 1u : 0u);
+          const bool pass = need & !fast;
+          diag::sb_stat_wave(9, __any(pass) ? 0u : 1u);
+          if (__any(pass)) sbmpc_cooperative<true>(pass && sub == 0, in, PT.sbmpc_nsamp, PT.sbmpc_dt, pb, cb);
+          // an accepted request's answer: the nominal scenario's (P_ca, Chi_ca), as the pass forms them
+          pb = fast ? p_ca_of(kSbNominalP) : pb;
+          cb = fast ? (-30.0 + 10.0 * kSbNominalChi) * (kPi / 180.0) : cb;
+        } else
         sbmpc_cooperative<true>(need && sub == 0, in, PT.sbmpc_nsamp, PT.sbmpc_dt, pb, cb);
         pb = env_lane_d<LPE, 0>(pb, env_lane0);
         cb = env_lane_d<LPE, 0>(cb, env_lane0);
@@ -2203,6 +2239,28 @@ __global__ __launch_bounds__(64) void sbmpc_eval_kernel(int n, double tf, double
     out[(size_t)i * 3 + 1] = active ? cb : 0.0;
     out[(size_t)i * 3 + 2] = active ? 1.0 : 0.0;
   }
+}
+
+// sbmpc_nominal_holds (shipsim_sbmpc_nominal.hpp) over shipsim_sbmpc_eval's request rows (shipsim_sbmpc_nominal): one
+// request per lane, reachable for requests the streams' trajectories never form. flag_out[i] bit 0: the test with
+// sin / cos(chi_d); bit 1: the form the streams' tick evaluates (sbmpc_nominal_holds_seg), on the course split into
+// a segment angle and a correction's argument by sbmpc_nominal_split_course.
+__global__ __launch_bounds__(64) void sbmpc_nominal_kernel(int n, double tf, double dt, const double* __restrict__ in,
+                                                           int32_t* __restrict__ flag_out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const double* r = in + (size_t)i * SHIPSIM_SBMPC_IN;
+  SbIn q;
+  q.p_last = r[0]; q.chi_last = r[1]; q.u_d = r[2]; q.chi_d = r[3];
+  q.os_x = r[4]; q.os_y = r[5]; q.os_v = r[8];
+  q.ob_x = r[10]; q.ob_y = r[11]; q.ob_psi = r[12]; q.ob_u = r[13]; q.ob_v = r[14];
+  sb_set_heading_trig(q);
+  q.obs_l = r[15]; q.obs_w = r[16];
+  double seg_sin, seg_cos, a;
+  sbmpc_nominal_split_course(q.chi_d, seg_sin, seg_cos, a);
+  const int n_samp = (int)(tf / dt);
+  flag_out[i] = (sbmpc_nominal_holds(q, n_samp, dt).holds ? 1 : 0) |
+                (sbmpc_nominal_holds_seg(q, seg_sin, seg_cos, a, n_samp, dt).holds ? 2 : 0);
 }
 
 // SBMPC.get_optimal_ctrl_offset over a do_list of n_obs obstacles (sbmpc.py:113-185) for n independent requests
@@ -3119,6 +3177,14 @@ int shipsim_sbmpc_eval(int32_t n, double tf, double dt, const double* in, double
   return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
 }
 
+int shipsim_sbmpc_nominal(int32_t n, double tf, double dt, const double* in, int32_t* flag_out, void* stream) {
+  if (n < 0 || (n > 0 && (!in || !flag_out)) || !(dt > 0) || tf / dt > 4096) return SHIPSIM_EINVAL;
+  if (n == 0) return SHIPSIM_OK;
+  hipLaunchKernelGGL(sbmpc_nominal_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, tf, dt, in,
+                     flag_out);
+  return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
+}
+
 int shipsim_sbmpc_eval_multi(int32_t n, int32_t n_obs, double tf, double dt, const double* in, double* out,
                              void* stream) {
   if (n < 0 || n_obs < 1 || n_obs > SHIPSIM_MAX_OBS || (n > 0 && (!in || !out)) || !(dt > 0) || tf / dt > 4096)
@@ -3182,9 +3248,13 @@ int shipsim_diag_lane_faults(uint32_t* out32) {
   return SHIPSIM_OK;
 #elif defined(SHIPSIM_SB_STATS)
   if (hipDeviceSynchronize() != hipSuccess) return SHIPSIM_EHIP;
-  if (hipMemcpyFromSymbol(out32 + 16, HIP_SYMBOL(diag::g_sb_stats), 8 * sizeof(uint64_t)) != hipSuccess)
-    return SHIPSIM_EHIP;
-  const uint64_t zero[8] = {};
+  // counters 0..7 in out32[16..31] (as before), the later ones from out32[0] on
+  uint64_t v[diag::kSbStats];
+  static_assert(diag::kSbStats >= 8 && diag::kSbStats <= 16, "the read-out's 32 words");
+  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(diag::g_sb_stats), sizeof(v)) != hipSuccess) return SHIPSIM_EHIP;
+  memcpy(out32 + 16, v, 8 * sizeof(uint64_t));
+  memcpy(out32, v + 8, (diag::kSbStats - 8) * sizeof(uint64_t));
+  const uint64_t zero[diag::kSbStats] = {};
   if (hipMemcpyToSymbol(HIP_SYMBOL(diag::g_sb_stats), zero, sizeof(zero)) != hipSuccess) return SHIPSIM_EHIP;
   return SHIPSIM_OK;
 #else

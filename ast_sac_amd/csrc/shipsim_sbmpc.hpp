@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "shipsim_device.hpp"
+#include "shipsim_sbmpc_nominal.hpp"  // SbIn, p_ca_of, sbmpc_h2, sbmpc_nominal_holds
 
 using namespace shipsim;
 
@@ -12,10 +13,7 @@ using namespace shipsim;
 // SBMPC (sbmpc.py:113-298), wave-cooperative: each requesting env's 7 x 4 scenarios are spread
 // over 28 lanes of a half-wave; two envs are served per pass.
 // ---------------------------------------------------------------------------------------------
-struct SbIn {
-  double u_d, chi_d, os_x, os_y, os_v, ob_x, ob_y, ob_psi, ob_u, ob_v, obs_l, obs_w, p_last, chi_last;
-  double ob_so, ob_co;  // sin / cos(ob_psi): the AST kernels pass the obstacle ship's carried sin/cos(yaw)
-};
+// (SbIn, the request, with p_ca_of and sbmpc_h2: shipsim_sbmpc_nominal.hpp, shared with the host)
 // sin/cos(ob_psi) of a request built from its heading alone
 __device__ __forceinline__ void sb_set_heading_trig(SbIn& q) { sincos(q.ob_psi, &q.ob_so, &q.ob_co); }
 
@@ -146,22 +144,6 @@ __device__ __forceinline__ double sbmpc_scenario_cost_direct(const SbIn& in, int
   return H1 + H2;
 }
 
-
-// SBMPCParams.P_ca_ = [0.4, 0.6, 0.8, 1.0] (sbmpc.py:36) by selects: a per-lane indexed constant array would be
-// a memory load on the scenario's critical path
-__device__ __forceinline__ double p_ca_of(int jp) {
-  return jp == 0 ? 0.4 : (jp == 1 ? 0.6 : (jp == 2 ? 0.8 : 1.0));
-}
-
-// the scenario's own terms of the cost (sbmpc.py:200-214: P_ca, Chi_ca and their changes); the whole
-// cost when no obstacle sample comes within max_d_safe
-__device__ __forceinline__ double sbmpc_h2(const SbIn& in, int ichi, int jp) {
-  const double P_ca = p_ca_of(jp);
-  const double Chi_ca = (-30.0 + 10.0 * ichi) * (kPi / 180.0);
-  const double dChi0 = Chi_ca - in.chi_last;
-  return 25 * (1 - P_ca) + 30 * (Chi_ca * Chi_ca) + 20 * fabs(in.p_last - P_ca) +
-         ((dChi0 > 0) ? 20 * dChi0 * dChi0 : (dChi0 < 0 ? 30 * dChi0 * dChi0 : 0));
-}
 
 // No scenario can bring this obstacle within max_d_safe over the horizon: the distance now minus the
 // most either ship can travel (own ship: sample 0 at its current sway, then straight at <= u_d; the

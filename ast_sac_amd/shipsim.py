@@ -82,7 +82,8 @@ def load_library(path=LIB_PATH):
                            ("shipsim_archive_workspace_bytes", [C.c_int32]),
                            ("shipsim_archive_elect", [C.c_int32, C.c_int32, P, P, P, P, P, C.c_int64, P, P, P]),
                            ("shipsim_set_stream_grouping", [P, C.c_int32]),
-                           ("shipsim_get_stream_grouping", [P, P])):
+                           ("shipsim_get_stream_grouping", [P, P]),
+                           ("shipsim_sbmpc_nominal", [C.c_int32, C.c_double, C.c_double, P, P, P])):
         try:
             getattr(L, name).argtypes = argtypes
             if name in ("shipsim_state_bytes", "shipsim_resample_workspace_bytes", "shipsim_archive_bytes",
@@ -113,7 +114,7 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_resample_workspace_bytes", "shipsim_resample", "shipsim_level_distance",
                     "shipsim_archive_bytes", "shipsim_archive_store", "shipsim_archive_load",
                     "shipsim_archive_workspace_bytes", "shipsim_archive_elect", "shipsim_set_stream_grouping",
-                    "shipsim_get_stream_grouping")
+                    "shipsim_get_stream_grouping", "shipsim_sbmpc_nominal")
 
 
 class Snapshot:
@@ -641,6 +642,24 @@ def sbmpc_eval(requests, tf=1000.0, dt=20.0, device="cuda"):
     rc = L.shipsim_sbmpc_eval(int(x.shape[0]), float(tf), float(dt), _ptr(x), _ptr(out), C.c_void_p(stream.cuda_stream))
     if rc:
         raise ShipSimError(f"shipsim_sbmpc_eval failed ({rc})")
+    return out
+
+
+def sbmpc_nominal(requests, tf=1000.0, dt=20.0, device="cuda"):
+    """The streams' pass-free test on the device for a batch of (n, 17) sbmpc_eval requests -> (n,) int32 tensor of
+    two bits, set where the nominal scenario provably wins, so that sbmpc_eval returns (1.0, 0.0, active): bit 0 by
+    the test on sin / cos(chi_d), bit 1 by the form the streams' tick evaluates, on the split course
+    (shipsim_sbmpc_nominal)."""
+    L = load_library()
+    x = torch.as_tensor(requests, dtype=torch.float64, device=device).contiguous()
+    if x.dim() != 2 or x.shape[1] != abi.SBMPC_IN:
+        raise ShipSimError(f"requests must be (n, {abi.SBMPC_IN})")
+    out = torch.zeros(x.shape[0], dtype=torch.int32, device=x.device)
+    stream = torch.cuda.current_stream(x.device)
+    rc = L.shipsim_sbmpc_nominal(int(x.shape[0]), float(tf), float(dt), _ptr(x), _ptr(out),
+                                 C.c_void_p(stream.cuda_stream))
+    if rc:
+        raise ShipSimError(f"shipsim_sbmpc_nominal failed ({rc})")
     return out
 
 

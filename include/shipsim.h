@@ -511,6 +511,17 @@ int shipsim_set_trajectory(shipsim_handle* h, double* ship_rows, double* env_row
 #define SHIPSIM_SBMPC_IN 17
 int shipsim_sbmpc_eval(int32_t n, double tf, double dt, const double* in, double* out, void* stream);
 
+/* The test by which the two-ship decision streams (collav sbmpc) answer a request without the optimiser's pass, for
+ * n of shipsim_sbmpc_eval's request rows (additive to ABI 12): flag_out[i] = 1 where the nominal scenario (speed
+ * factor 1, course offset 0) provably wins request i — the memory at (1, 0) and a closed-form upper bound on that
+ * scenario's collision cost below every other scenario's own terms (ast_sac_amd/csrc/shipsim_sbmpc_nominal.hpp) —
+ * else 0. For such a row shipsim_sbmpc_eval returns (1.0, 0.0, active). The D_INIT test of the request is not part
+ * of it. flag_out[i] holds two bits: bit 0 the test with the sine and cosine of chi_d; bit 1 the form the streams'
+ * tick evaluates (sbmpc_nominal_holds_seg: the course as a segment angle's sine and cosine with the argument of the
+ * LOS correction, no atan), on the split of chi_d that sbmpc_nominal_split_course defines. The two agree except
+ * within rounding of the decision. Device pointers (flag_out: n int32); stateless, asynchronous on `stream`. */
+int shipsim_sbmpc_nominal(int32_t n, double tf, double dt, const double* in, int32_t* flag_out, void* stream);
+
 /* SBMPC.get_optimal_ctrl_offset (sbmpc.py:113-185) over a do_list of n_obs dynamic obstacles (1 <= n_obs <=
  * SHIPSIM_MAX_OBS; active when any of them is within D_INIT, per scenario the worst obstacle's cost, the least worst
  * scenario: :149-178) for n independent requests, stateless like shipsim_sbmpc_eval (ABI 10). in: n x

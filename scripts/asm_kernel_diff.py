@@ -2,7 +2,8 @@
 a change that must not alter the device code). Kernels are matched by symbol, so their order in the file may differ.
 Compared per kernel: its text from its section directive (`.section .text.<name>`; `.text` for a kernel that is no
 template) to the end of its `.amdhsa_kernel` block, and its entry in the `amdhsa.kernels` metadata. Lines naming the
-`__hip_cuid_*` symbol are ignored (it hashes the source path).
+`__hip_cuid_*` symbol are ignored (it hashes the source path), and local labels are compared without the number of
+their function in the file.
 Usage: python scripts/asm_kernel_diff.py BEFORE.s AFTER.s   (exit status 1 if anything differs)"""
 import re
 import sys
@@ -10,6 +11,9 @@ import sys
 
 def kernels(path):
     lines = [l for l in open(path).read().split("\n") if "__hip_cuid_" not in l]
+    # (local labels carry the function's number in the file, .LBB<function>_<block>: a kernel added in front of
+    # others renumbers theirs without changing their code)
+    lines = [re.sub(r"[ \t]+;", " ;", re.sub(r"\bL?BB\d+_(\d+)", r"BB_\1", l)) for l in lines]  # (and comment padding)
     text, meta = {}, {}
     begin = re.compile(r"\s*\.protected\s+(\S+)\s*; -- Begin function")
     for i, l in enumerate(lines):

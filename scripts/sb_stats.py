@@ -6,7 +6,8 @@ on the GPU box:  SHIPSIM_LIB=ast_sac_amd/lib/abl/NAME.so python scripts/sb_stats
          from the synchronised reset, i.e. in the bench's timed regime
 The third argument is the stream grouping (shipsim_set_stream_grouping): on (the default), off, or both legs, one
 after the other, each on a fresh handle. Prints one JSON line per leg: per env-tick request rate, passes per optimiser
-call, lone-request share, requests per pass, horizons per pass (K > 1)."""
+call, lone-request share, requests per pass, horizons per pass (K > 1), and (K = 1) the share of the requests the
+nominal-scenario test answered without a pass with the passes per wave-tick that remain."""
 import ctypes as C
 import json
 import os
@@ -23,13 +24,15 @@ from ast_sac_amd import shipsim_abi as abi  # noqa: E402
 from ast_sac_amd.shipsim import ShipSim, load_library  # noqa: E402
 
 NAMES = ["wave_ticks_with_pass", "passes", "lone_passes", "requests_served", "horizon_lanes", "far_lanes",
-         "env_ticks_requesting", "env_ticks"]
+         "env_ticks_requesting", "env_ticks", "requests_answered_nominal", "wave_ticks_all_answered"]
 
 
 def read_stats(L):
     out = (C.c_uint32 * 32)()
     assert L.shipsim_diag_lane_faults(out) == 0, "not an SHIPSIM_SB_STATS build"
-    return [out[16 + 2 * i] | (out[17 + 2 * i] << 32) for i in range(8)]
+    # counters 0..7 in words 16..31, the later ones from word 0 on (shipsim_diag_lane_faults)
+    return [out[16 + 2 * i] | (out[17 + 2 * i] << 32) for i in range(8)] + \
+        [out[2 * i] | (out[2 * i + 1] << 32) for i in range(len(NAMES) - 8)]
 
 
 def headline(L, dev, launches, grouping, n_envs=4096, slice_ticks=4096, tail_ticks=1024):
@@ -81,6 +84,9 @@ def main():
                  requests_per_pass=v[3] / max(v[1], 1), horizon_lanes_per_pass=v[4] / max(v[1], 1),
                  far_lanes_per_pass=v[5] / max(v[1], 1), wave_ticks_with_pass_per_env_tick=v[0] / max(v[7], 1),
                  passes_per_env_tick=v[1] / max(v[7], 1))
+        if K == 1:  # (four envs per wave at 16 lanes per env: a wave-tick is four env-ticks)
+            d.update(nominal_share=v[8] / max(v[6], 1), passes_per_wave_tick=4.0 * v[1] / max(v[7], 1),
+                     requests_left_per_wave_tick=4.0 * (v[6] - v[8]) / max(v[7], 1))
         print(json.dumps(d), flush=True)
 
 
