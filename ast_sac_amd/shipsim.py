@@ -83,11 +83,20 @@ def load_library(path=LIB_PATH):
                            ("shipsim_archive_elect", [C.c_int32, C.c_int32, P, P, P, P, P, C.c_int64, P, P, P]),
                            ("shipsim_set_stream_grouping", [P, C.c_int32]),
                            ("shipsim_get_stream_grouping", [P, P]),
-                           ("shipsim_sbmpc_nominal", [C.c_int32, C.c_double, C.c_double, P, P, P])):
+                           ("shipsim_sbmpc_nominal", [C.c_int32, C.c_double, C.c_double, P, P, P]),
+                           ("shipsim_tree_bytes", [C.c_int32, C.c_int32]),
+                           ("shipsim_tree_layout", [C.c_int32, C.c_int32, P]),
+                           ("shipsim_tree_workspace_bytes", [C.c_int32, C.c_int32]),
+                           ("shipsim_tree_init", [P, C.c_int64, C.c_int32, C.c_int32, P]),
+                           ("shipsim_tree_select", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_double, P, C.c_int64, P, P, P]),
+                           ("shipsim_tree_expand", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P, P, C.c_int64,
+                                                    P, P]),
+                           ("shipsim_tree_backup", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P, P])):
         try:
             getattr(L, name).argtypes = argtypes
             if name in ("shipsim_state_bytes", "shipsim_resample_workspace_bytes", "shipsim_archive_bytes",
-                        "shipsim_archive_workspace_bytes"):
+                        "shipsim_archive_workspace_bytes", "shipsim_tree_bytes", "shipsim_tree_workspace_bytes"):
                 getattr(L, name).restype = C.c_int64
         except AttributeError:
             if "SHIPSIM_LIB" not in os.environ:
@@ -114,7 +123,9 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_resample_workspace_bytes", "shipsim_resample", "shipsim_level_distance",
                     "shipsim_archive_bytes", "shipsim_archive_store", "shipsim_archive_load",
                     "shipsim_archive_workspace_bytes", "shipsim_archive_elect", "shipsim_set_stream_grouping",
-                    "shipsim_get_stream_grouping", "shipsim_sbmpc_nominal")
+                    "shipsim_get_stream_grouping", "shipsim_sbmpc_nominal", "shipsim_tree_bytes", "shipsim_tree_layout",
+                    "shipsim_tree_workspace_bytes", "shipsim_tree_init", "shipsim_tree_select", "shipsim_tree_expand",
+                    "shipsim_tree_backup")
 
 
 class Snapshot:
@@ -785,3 +796,119 @@ def archive_elect(cell, score, cell_score, cell_seen=None, workspace=None, out_e
     if rc:
         raise ShipSimError(f"shipsim_archive_elect failed ({rc})")
     return eoc, k_out
+
+
+TREE_MAX_CHILDREN, TREE_MAX_DEPTH, TREE_MAX_WORKERS = abi.TREE_MAX_CHILDREN, abi.TREE_MAX_DEPTH, abi.TREE_MAX_WORKERS
+TREE_FIELDS = ("header", "parent", "depth", "n_children", "child", "visits", "value_sum", "action", "flags")
+_TREE_DTYPES = dict(header=torch.int32, parent=torch.int32, depth=torch.int32, n_children=torch.int32, child=torch.int32,
+                    visits=torch.int32, value_sum=torch.int64, action=torch.float32, flags=torch.int32)
+
+
+def tree_layout(max_nodes, max_children):
+    """Byte offsets of a tree buffer's arrays (shipsim_tree_layout): dict over TREE_FIELDS, and 'bytes', its size."""
+    out = (C.c_int64 * 10)()
+    if load_library().shipsim_tree_layout(int(max_nodes), int(max_children), out):
+        raise ShipSimError(f"tree: max_nodes must be in 1..{ARCHIVE_MAX_CELLS} and max_children in "
+                           f"1..{TREE_MAX_CHILDREN}, not {max_nodes} and {max_children}")
+    return dict(zip(TREE_FIELDS + ("bytes",), (int(v) for v in out)))
+
+
+class SearchTree:
+    """A search tree on the device (include/shipsim.h: shipsim_tree_*): `data`, the tree buffer as a uint8 tensor;
+    its arrays as tensors that share its memory — header (int32[4]: n_nodes, dropped, skipped), parent, depth,
+    n_children, child (max_nodes, max_children), visits, value_sum (int64, 24 fractional bits), action, flags — and
+    the workspace of its calls, sized for n_workers. Node i is cell i of a StateArchive of max_nodes cells. Made with
+    the one-node tree in it; every method is asynchronous on the current stream, allocates nothing and can be
+    captured into a graph."""
+
+    def __init__(self, max_nodes, max_children, n_workers, device="cuda"):
+        L = load_library()
+        self.max_nodes, self.max_children, self.n_workers = int(max_nodes), int(max_children), int(n_workers)
+        self.layout = tree_layout(self.max_nodes, self.max_children)
+        if not 1 <= self.n_workers <= TREE_MAX_WORKERS:
+            raise ShipSimError(f"tree: n_workers must be in 1..{TREE_MAX_WORKERS}, not {n_workers}")
+        self.device = dev = torch.device(device)
+        if dev.index is None:
+            self.device = dev = torch.device(dev.type, torch.cuda.current_device())
+        self.data = torch.zeros(self.layout["bytes"], dtype=torch.uint8, device=dev)
+        M, Cc = self.max_nodes, self.max_children
+        for name in TREE_FIELDS:
+            dt = _TREE_DTYPES[name]
+            count = dict(header=4, child=M * Cc).get(name, M)
+            o = self.layout[name]
+            setattr(self, name, self.data[o:o + count * dt.itemsize].view(dt))
+        self.child = self.child.view(M, Cc)
+        self.workspace = torch.empty(int(L.shipsim_tree_workspace_bytes(M, self.n_workers)), dtype=torch.uint8, device=dev)
+        self.leaf = torch.empty(self.n_workers, dtype=torch.int32, device=dev)
+        self.expand_flag = torch.empty(self.n_workers, dtype=torch.int32, device=dev)
+        self.node = torch.empty(self.n_workers, dtype=torch.int32, device=dev)
+        self.init()
+
+    def _call(self, name, *args):
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = getattr(load_library(), name)(_ptr(self.data), self.data.numel(), self.max_nodes, self.max_children,
+                                               *args, C.c_void_p(stream.cuda_stream))
+        if rc:
+            raise ShipSimError(f"{name} failed ({rc})")
+
+    def _arg(self, x, dtype, what):
+        t = torch.as_tensor(x, dtype=dtype, device=self.device).contiguous().reshape(-1)
+        if t.numel() != self.n_workers:
+            raise ShipSimError(f"tree {what}: {t.numel()} entries for {self.n_workers} workers")
+        return t
+
+    def init(self):
+        """The one-node tree: the root, node 0 (shipsim_tree_init)."""
+        self._call("shipsim_tree_init")
+
+    def select(self, max_depth, widen=(1, 1), c_explore=1.0):
+        """Where each of the n_workers workers starts this round (shipsim_tree_select): (leaf, expand), int32 tensors
+        owned by the tree — worker w starts from node leaf[w] and creates a child there iff expand[w] == 1."""
+        c = float(c_explore)
+        if not (c >= 0.0 and c != float("inf")):
+            raise ShipSimError(f"tree select: c_explore must be finite and >= 0, not {c_explore}")
+        self._call("shipsim_tree_select", self.n_workers, int(max_depth), int(widen[0]), int(widen[1]), C.c_double(c),
+                   _ptr(self.workspace), self.workspace.numel(), _ptr(self.leaf), _ptr(self.expand_flag))
+        return self.leaf, self.expand_flag
+
+    def expand(self, action, leaf=None, expand=None):
+        """The widening workers' new nodes (shipsim_tree_expand; leaf, expand: select's, by default the last ones):
+        node, an int32 tensor owned by the tree — the new id, leaf[w] for a worker that did not widen, -1 where the
+        pool was full."""
+        leaf = self.leaf if leaf is None else self._arg(leaf, torch.int32, "expand")
+        expand = self.expand_flag if expand is None else self._arg(expand, torch.int32, "expand")
+        a = self._arg(action, torch.float32, "expand")
+        self._call("shipsim_tree_expand", self.n_workers, _ptr(leaf), _ptr(expand), _ptr(a), _ptr(self.workspace),
+                   self.workspace.numel(), _ptr(self.node))
+        self._keep = (leaf, expand, a)
+        return self.node
+
+    def backup(self, value, node=None, terminal=None):
+        """visits += 1 and value_sum += round(value[w] * 2^24) from node[w] (default: the last expand's) up to the
+        root (shipsim_tree_backup); terminal: optional per-worker flags, the terminal bit of node[w]."""
+        node = self.node if node is None else self._arg(node, torch.int32, "backup")
+        v = self._arg(value, torch.float64, "backup")
+        t = None if terminal is None else self._arg(terminal, torch.uint8, "backup")
+        self._call("shipsim_tree_backup", self.n_workers, _ptr(node), _ptr(v), _ptr(t))
+        self._keep = (node, v, t)
+
+    @property
+    def n_nodes(self):
+        """The node count (one copy to the host)."""
+        return int(self.header[0].item())
+
+
+def tree_select(tree, max_depth, widen=(1, 1), c_explore=1.0):
+    """SearchTree.select as a function: (leaf, expand)."""
+    return tree.select(max_depth, widen, c_explore)
+
+
+def tree_expand(tree, action, leaf=None, expand=None):
+    """SearchTree.expand as a function: node."""
+    return tree.expand(action, leaf, expand)
+
+
+def tree_backup(tree, value, node=None, terminal=None):
+    """SearchTree.backup as a function."""
+    return tree.backup(value, node, terminal)

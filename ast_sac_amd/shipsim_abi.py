@@ -98,6 +98,10 @@ TE_FLAG_COLLISION, TE_FLAG_IMMINENT = 1, 2
 SBMPC_IN = 17
 SBMPC_MULTI_IN = 10 + 7 * MAX_OBS  # shipsim_sbmpc_eval_multi rows (include/shipsim.h)
 ARCHIVE_MAX_CELLS = 1 << 22  # SHIPSIM_ARCHIVE_MAX_CELLS: the most cells of a state archive
+TREE_MAX_CHILDREN = 64  # SHIPSIM_TREE_MAX_CHILDREN: the most children of a search-tree node
+TREE_MAX_DEPTH = 32  # SHIPSIM_TREE_MAX_DEPTH
+TREE_MAX_WORKERS = 1 << 22  # SHIPSIM_TREE_MAX_WORKERS: the most workers of one select / expand / backup
+TREE_SCAN_TILE = 1024  # SHIPSIM_TREE_SCAN_TILE
 
 
 def events_to_string(bits):

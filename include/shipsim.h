@@ -453,6 +453,72 @@ int shipsim_archive_elect(int32_t n_envs, int32_t n_cells, const int32_t* cell, 
                           double* cell_score, int32_t* cell_seen, void* workspace, int64_t workspace_bytes,
                           int32_t* env_of_cell_out, int32_t* n_improved_out, void* stream);
 
+/* ---- search tree over archived states: select, expand, back up (additive to ABI 12) ------------------------------
+ * The env is deterministic given its action sequence, so a node of the tree is a state: node id i is cell i of a
+ * state archive of max_nodes cells, and only actions are widened progressively. A tree is a caller-owned device
+ * buffer, 16-byte aligned, of shipsim_tree_bytes(max_nodes, max_children) bytes: max_nodes in
+ * 1..SHIPSIM_ARCHIVE_MAX_CELLS, max_children (C) in 1..SHIPSIM_TREE_MAX_CHILDREN. It is a structure of arrays whose
+ * byte offsets shipsim_tree_layout writes into offsets_out[SHIPSIM_TREE_LAYOUT_FIELDS], in this order:
+ *   header      int32[4]: n_nodes; dropped, the new nodes the pool had no room for; skipped, the backups not taken; 0
+ *   parent      int32 [max_nodes], -1 for the root        depth      int32 [max_nodes]
+ *   n_children  int32 [max_nodes]                         child      int32 [max_nodes * C], in creation order
+ *   visits      int32 [max_nodes]                         value_sum  int64 [max_nodes], round(value * 2^24) summed
+ *   action      float32 [max_nodes], the edge from the parent         flags  int32 [max_nodes], bit 0: terminal
+ *   and the buffer's size.
+ * The calls are stateless like shipsim_archive_elect: no handle, device pointers, asynchronous on `stream` (a
+ * hipStream_t, NULL for the default stream), no allocation and no host synchronisation, so that a linear graph can
+ * capture them. What their launches hand one another lives in `workspace`, a caller-owned device buffer, 16-byte
+ * aligned, of at least shipsim_tree_workspace_bytes(max_nodes, n_workers) bytes, which does not decrease in either
+ * argument; select and expand of one round may share it. n_workers (W) is in 1..SHIPSIM_TREE_MAX_WORKERS.
+ *
+ * shipsim_tree_init writes the one-node tree: the root, node 0, and zero counters.
+ *
+ * shipsim_tree_select sends W interchangeable workers down the tree, "one after the other from the root, each seeing
+ * the virtual visits of those before it". The t-th worker (t = 0, 1, ...) to arrive at node v in this call:
+ *   - stays at v if v is terminal or depth(v) == max_depth (0..SHIPSIM_TREE_MAX_DEPTH); otherwise, with
+ *     m = n_children(v) + the children being created at v in this call and N = visits(v) + t,
+ *   - widens v iff m < C and (u64)m * m * wden < (u64)wnum * (N + 1), that is m < k * sqrt(N + 1) with
+ *     k^2 = wnum / wden (both in 1..2^15), and is then counted among the children being created;
+ *   - otherwise stays at v if v has no child;
+ *   - otherwise goes to the child a of the largest score, ties to the lowest child slot, and counts as arrived at a:
+ *       Q_a   = visits(a) > 0 ? ldexp((double)value_sum(a) / (double)visits(a), -24) : 0.0
+ *       score = Q_a + (c_explore * sqrt((double)(N + 1))) / (double)(1 + visits(a) + arrived_a)
+ *     five IEEE operations in this order, without contraction. Children being created in this call are no candidates.
+ * Output: nodes by increasing id; per node its staying workers, then its widening ones. Worker w starts from the
+ * state of node leaf_out[w] and creates a child there iff expand_out[w] == 1. The tree is not written.
+ *
+ * shipsim_tree_expand takes select's leaf and expand arrays (the widening workers of one node adjacent, as select
+ * emits them) and an action per worker. The widening workers get the ids n_nodes + rank in worker order; a new node
+ * has its parent, depth + 1, action[w] and zero statistics, and is appended to its parent's child[] in worker order;
+ * n_nodes advances. An id >= max_nodes is dropped: node_out[w] = -1 and dropped += 1 (as for a widening worker whose
+ * leaf names no node or no free child slot). Every other worker gets node_out[w] = leaf[w].
+ *
+ * shipsim_tree_backup adds one value along the whole path: q = (int64)nearbyint(ldexp(value[w], 24)) clamped to
+ * +-2^40, and every node from node[w] up to the root gets visits += 1 and value_sum += q (integer atomics: the
+ * result does not depend on the order). A worker with node[w] outside the tree (-1: dropped) or a non-finite value is
+ * skipped: skipped += 1. terminal (may be NULL): terminal[w] != 0 ORs the terminal bit into node[w].
+ *
+ * SHIPSIM_EINVAL, before any device call: a NULL tree, workspace or required array; sizes out of range;
+ * tree_bytes != shipsim_tree_bytes(...); a tree or workspace not 16-byte aligned; a workspace too small; c_explore
+ * negative or not finite. The arithmetic is ast_sac_amd/csrc/shipsim_tree_host.hpp, restated in tests/tree_ref.py. */
+#define SHIPSIM_TREE_MAX_CHILDREN 64
+#define SHIPSIM_TREE_MAX_DEPTH 32
+#define SHIPSIM_TREE_MAX_WORKERS (1 << 22)
+#define SHIPSIM_TREE_SCAN_TILE 1024 /* nodes numbered by one block of select's scan */
+#define SHIPSIM_TREE_LAYOUT_FIELDS 10
+int64_t shipsim_tree_bytes(int32_t max_nodes, int32_t max_children);
+int shipsim_tree_layout(int32_t max_nodes, int32_t max_children, int64_t* offsets_out);
+int64_t shipsim_tree_workspace_bytes(int32_t max_nodes, int32_t n_workers);
+int shipsim_tree_init(void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children, void* stream);
+int shipsim_tree_select(const void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children,
+                        int32_t n_workers, int32_t max_depth, int32_t wnum, int32_t wden, double c_explore,
+                        void* workspace, int64_t workspace_bytes, int32_t* leaf_out, int32_t* expand_out, void* stream);
+int shipsim_tree_expand(void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children, int32_t n_workers,
+                        const int32_t* leaf, const int32_t* expand, const float* action, void* workspace,
+                        int64_t workspace_bytes, int32_t* node_out, void* stream);
+int shipsim_tree_backup(void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children, int32_t n_workers,
+                        const int32_t* node, const double* value, const uint8_t* terminal, void* stream);
+
 /* ---- trajectory recording (f1: simulation_results export) ----------------------------------
  * Per-tick rows of ShipModelAST/SimpleShipModel.store_simulation_data (ship_model.py:903-957,
  * run_colav/.../ship_model.py:418-444) for both ships, plus the RewardTracker entry of every tick
