@@ -17,7 +17,8 @@ SOURCES = {
                 "ast_sac_amd/csrc/shipsim_resample.hip", "ast_sac_amd/csrc/shipsim_resample_host.hpp",
                 "ast_sac_amd/csrc/shipsim_archive.hip", "ast_sac_amd/csrc/shipsim_archive_host.hpp",
                 "ast_sac_amd/csrc/shipsim_grouping_host.hpp", "ast_sac_amd/csrc/shipsim_sbmpc_nominal.hpp",
-                "ast_sac_amd/csrc/shipsim_tree.hip", "ast_sac_amd/csrc/shipsim_tree_host.hpp"],
+                "ast_sac_amd/csrc/shipsim_tree.hip", "ast_sac_amd/csrc/shipsim_tree_host.hpp",
+                "ast_sac_amd/csrc/shipsim_weather.hip"],
     "sacfused": ["ast_sac_amd/csrc/sac_kernels.hip", "include/sac_fused.h"],
 }
 
@@ -34,7 +35,7 @@ HIPFLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shar
 # r4z_sched_ab.txt), with the scheduler's AMDGPU register-pressure trackers (+0.5 %, r4zz_sched3_ab.txt).
 LIB_FLAGS = {"shipsim": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-mllvm", "-amdgpu-use-amdgpu-trackers"],
              "sacfused": []}
-# The libraries are linked from two to five objects, each a (source file, extra flags) pair.
+# The libraries are linked from two to six objects, each a (source file, extra flags) pair.
 # sacfused: max-ILP is 0.6 µs faster per grad step at H = 256 but spills SGPRs in three kernels at H = 448 / 512,
 # so the widths up to 384 (and the C ABI) are one object with it and the two widest another without: two objects of
 # the same source (sac_kernels.hip SACF_TU).
@@ -42,14 +43,16 @@ LIB_FLAGS = {"shipsim": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-mllvm", "
 # (above); the C2 three-wave kernel is a source of its own that keeps it — its loops have registers to spare, and
 # hoisting the fp64 constants of atan / sincos out of the tick loop shortens the tick. The resampling kernels
 # (shipsim_resample / shipsim_level_distance) are a third object, with the library's flags alone, and the state
-# archive's (shipsim_archive_store / _load / _elect) a fourth and the search tree's (shipsim_tree_*) a fifth, the same way.
+# archive's (shipsim_archive_store / _load / _elect) a fourth and the search tree's (shipsim_tree_*) a fifth, the same way, and
+# the gather that moves per-env weather (shipsim_weather_store / _load / _fork) a sixth.
 OBJECTS = {"sacfused": [("ast_sac_amd/csrc/sac_kernels.hip", ["-DSACF_TU=1", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
                         ("ast_sac_amd/csrc/sac_kernels.hip", ["-DSACF_TU=2"])],
            "shipsim": [("ast_sac_amd/csrc/shipsim_kernels.hip", ["-mllvm", "-disable-machine-licm"]),
                        ("ast_sac_amd/csrc/shipsim_c2_pipe.hip", []),
                        ("ast_sac_amd/csrc/shipsim_resample.hip", []),
                        ("ast_sac_amd/csrc/shipsim_archive.hip", []),
-                       ("ast_sac_amd/csrc/shipsim_tree.hip", [])]}
+                       ("ast_sac_amd/csrc/shipsim_tree.hip", []),
+                       ("ast_sac_amd/csrc/shipsim_weather.hip", [])]}
 
 
 def lib_objects(lib):

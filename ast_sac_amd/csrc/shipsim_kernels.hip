@@ -2406,13 +2406,19 @@ struct shipsim_handle {
   int lpe;  // lanes per AST env of the step / stream kernels (lanes_per_env)
   int32_t tail_extra;  // shipsim_set_stream_tail (0: off)
   int32_t* tail_ctr;   // its device counter (one int, zeroed before every stream launch)
-  // shipsim_set_weather: the per-env weather array on the device (kWeatherCols x n_envs, an allocation of its own),
-  // the caller's four arrays as given (4 x n_envs, host: shipsim_get_weather), whether the handle runs on them,
-  // and the lanes per env the handle runs without them (lpe while they are set: the nearest weather kernel's)
+  // shipsim_set_weather: the per-env weather table on the device (weather_host::kStoreRows x n_envs, an allocation of
+  // its own: the kWeatherCols rows the kernels read, then the wind direction as set), the caller's four arrays as
+  // given (4 x n_envs, host: shipsim_get_weather), whether the handle runs on them, and the lanes per env the
+  // handle runs without them (lpe while they are set: the nearest weather kernel's)
   double* wx_dev;
   double* wx_host;
   int wx_on;
   int lpe_uniform;
+  // shipsim_weather_fork gathers into this table of the same size and copies it back (allocated with wx_dev); and
+  // whether a weather_store / _load / _fork has ever been called on the handle, a capture included: from then on the
+  // device table, which a graph replay changes without a host call, is what shipsim_get_weather reads
+  double* wx_stage;
+  int wx_moved;
   // shipsim_fork from the live state gathers into this block of dev_bytes and copies it back (allocated at the
   // first such call)
   void* fork_block;
@@ -2700,6 +2706,7 @@ int shipsim_destroy(shipsim_handle* h) {
     if (h->nonfinite_dev) (void)hipFree(h->nonfinite_dev);
     if (h->tail_ctr) (void)hipFree(h->tail_ctr);
     if (h->wx_dev) (void)hipFree(h->wx_dev);
+    if (h->wx_stage) (void)hipFree(h->wx_stage);
     if (h->fork_block) (void)hipFree(h->fork_block);
     if (h->slot_env) (void)hipFree(h->slot_env);
   }
@@ -3118,7 +3125,8 @@ int shipsim_set_weather(shipsim_handle* h, const double* wind_speed, const doubl
     return fail(h, SHIPSIM_EINVAL, "set_weather: env %lld: wind speed %g, wind direction %g, current (%g, %g) "
                 "(finite values and a wind speed >= 0)", (long long)bad, wind_speed[bad], wind_direction[bad],
                 current_from_north[bad], current_from_east[bad]);
-  double* dev_rows = (double*)malloc(sizeof(double) * kWeatherCols * n);
+  const size_t table_bytes = (size_t)weather_host::store_bytes((int64_t)n);
+  double* dev_rows = (double*)malloc(table_bytes);
   double* host = h->wx_host ? h->wx_host : (double*)malloc(sizeof(double) * 4 * n);
   if (!dev_rows || !host) {
     free(dev_rows);
@@ -3126,20 +3134,24 @@ int shipsim_set_weather(shipsim_handle* h, const double* wind_speed, const doubl
     return fail(h, SHIPSIM_ENOMEM, "set_weather: out of host memory");
   }
   DeviceGuard g(h->device);
-  if (!h->wx_dev) {
-    hipError_t e = hipMalloc(&h->wx_dev, sizeof(double) * kWeatherCols * n);
+  if (!h->wx_dev) {  // the table and shipsim_weather_fork's staging table: nothing allocates after this
+    hipError_t e = hipMalloc(&h->wx_dev, table_bytes);
+    if (e == hipSuccess) {
+      e = hipMalloc(&h->wx_stage, table_bytes);
+      if (e != hipSuccess) (void)hipFree(h->wx_dev);
+    }
     if (e != hipSuccess) {
       free(dev_rows);
       if (!h->wx_host) free(host);
-      h->wx_dev = nullptr;
+      h->wx_dev = h->wx_stage = nullptr;
       return fail(h, SHIPSIM_EHIP, "hipMalloc(weather): %s", hipGetErrorString(e));
     }
   }
   h->wx_host = host;
-  weather_host::rows(wind_speed, wind_direction, current_from_north, current_from_east, n, dev_rows);
+  weather_host::store_rows(wind_speed, wind_direction, current_from_north, current_from_east, n, dev_rows);
   // the upload is ordered on the handle's stream behind the launches already queued, and complete on return
   // (the staging rows are freed here): a change takes effect at the next launch
-  hipError_t e = hipMemcpyAsync(h->wx_dev, dev_rows, sizeof(double) * kWeatherCols * n, hipMemcpyHostToDevice, h->stream);
+  hipError_t e = hipMemcpyAsync(h->wx_dev, dev_rows, table_bytes, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   free(dev_rows);
   if (e != hipSuccess) {  // the device array is in an unknown state: the handle runs the config's weather
@@ -3165,8 +3177,69 @@ int shipsim_get_weather(shipsim_handle* h, double* wind_speed, double* wind_dire
   double* out[4] = {wind_speed, wind_direction, current_from_north, current_from_east};
   const double uniform[4] = {h->cfg.wind_speed, h->cfg.wind_direction, h->cfg.current_velocity_component_from_north,
                              h->cfg.current_velocity_component_from_east};
+  if (h->wx_on && h->wx_moved) {
+    // weather has moved on the device, maybe by a graph replay that made no host call: the table is the record.
+    // Wait for what is queued, then read the four rows the caller set (the direction from its own row).
+    static const int row_of[4] = {weather_host::kWindSpeed, weather_host::kDirection, weather_host::kCurrentN,
+                                  weather_host::kCurrentE};
+    DeviceGuard g(h->device);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 4; ++k)
+      HIPCHK(h, hipMemcpy(out[k], h->wx_dev + (size_t)row_of[k] * n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return SHIPSIM_OK;
+  }
   for (int k = 0; k < 4; ++k)
     for (size_t i = 0; i < n; ++i) out[k][i] = h->wx_on ? h->wx_host[k * n + i] : uniform[k];
+  return SHIPSIM_OK;
+}
+
+// ---- weather that moves with the state: the handle's table gathered by index (the kernel is shipsim_weather.hip's,
+// the sizes and the refusals shipsim_weather_host.hpp's) ----
+int64_t shipsim_weather_bytes(int32_t n_slots) {
+  return weather_host::slots_ok(n_slots) ? weather_host::store_bytes(n_slots) : SHIPSIM_EINVAL;
+}
+
+int shipsim_weather_store(shipsim_handle* h, void* wx, int64_t bytes, int32_t n_slots, const int32_t* env_of_slot) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (const char* why = weather_host::carry_refusal(h->wx_on, wx, bytes, n_slots, h->P.n_envs, env_of_slot))
+    return fail(h, SHIPSIM_EINVAL, "weather_store: %s", why);
+  DeviceGuard g(h->device);
+  h->wx_moved = 1;
+  if (!env_of_slot) {  // a weather snapshot
+    HIPCHK(h, hipMemcpyAsync(wx, h->wx_dev, (size_t)bytes, hipMemcpyDeviceToDevice, h->stream));
+    return SHIPSIM_OK;
+  }
+  shipsim_weather_gather_launch(h->stream, h->wx_dev, (double*)wx, env_of_slot, n_slots, h->P.n_envs, false);
+  HIPCHK(h, hipGetLastError());
+  return SHIPSIM_OK;
+}
+
+int shipsim_weather_load(shipsim_handle* h, const void* wx, int64_t bytes, int32_t n_slots, const int32_t* slot_of_env) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (const char* why = weather_host::carry_refusal(h->wx_on, wx, bytes, n_slots, h->P.n_envs, slot_of_env))
+    return fail(h, SHIPSIM_EINVAL, "weather_load: %s", why);
+  DeviceGuard g(h->device);
+  h->wx_moved = 1;
+  if (!slot_of_env) {  // a restore
+    HIPCHK(h, hipMemcpyAsync(h->wx_dev, wx, (size_t)bytes, hipMemcpyDeviceToDevice, h->stream));
+    return SHIPSIM_OK;
+  }
+  shipsim_weather_gather_launch(h->stream, (const double*)wx, h->wx_dev, slot_of_env, h->P.n_envs, n_slots, false);
+  HIPCHK(h, hipGetLastError());
+  return SHIPSIM_OK;
+}
+
+int shipsim_weather_fork(shipsim_handle* h, const int32_t* src_env) {
+  if (!h || !h->dev_block) return SHIPSIM_EINVAL;
+  if (const char* why = weather_host::fork_refusal(h->wx_on)) return fail(h, SHIPSIM_EINVAL, "weather_fork: %s", why);
+  if (!src_env) return SHIPSIM_OK;  // the identity: nothing moves
+  DeviceGuard g(h->device);
+  h->wx_moved = 1;
+  // gathered into the staging table and copied back, as shipsim_fork does with the state: the table never moves
+  shipsim_weather_gather_launch(h->stream, h->wx_dev, h->wx_stage, src_env, h->P.n_envs, h->P.n_envs, true);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(h->wx_dev, h->wx_stage, (size_t)weather_host::store_bytes(h->P.n_envs),
+                           hipMemcpyDeviceToDevice, h->stream));
   return SHIPSIM_OK;
 }
 

@@ -142,3 +142,9 @@ void shipsim_level_distance_launch(hipStream_t st, const DevState& S, int n_envs
 void shipsim_archive_gather_launch(hipStream_t st, const state_host::Table& src_table,
                                    const state_host::Table& dst_table, const void* src, void* dst,
                                    const int32_t* index, int32_t n_dst, int32_t n_src);
+
+// weather_gather_kernel (shipsim_weather.hip): slot d of the n_dst slots of the weather table dst takes slot index[d]
+// of the n_src slots of src, all six rows (weather_host::kStoreRows); an index outside [0, n_src) leaves slot d alone,
+// or — own, n_src == n_dst: a fork's staging table — gives it slot d of src
+void shipsim_weather_gather_launch(hipStream_t st, const double* src, double* dst, const int32_t* index, int32_t n_dst,
+                                   int32_t n_src, bool own);

@@ -100,26 +100,37 @@ class BatchedMultiShipRLEnv:
     def state_bytes(self):
         return self.sim.state_bytes
 
-    def snapshot(self, out=None):
+    def snapshot(self, out=None, weather=False):
         """The complete state of every env (a shipsim.Snapshot on the device): what restore() and fork() continue
-        from, mid-decision state included. Weather, like the config, stays with the env object."""
-        return self.sim.snapshot(out=out)
+        from, mid-decision state included. Weather, like the config, stays with the env object, unless
+        weather=True: then the Snapshot also carries the per-env weather in force (its `weather`)."""
+        return self.sim.snapshot(out=out, weather=weather)
 
-    def restore(self, snap):
-        """Rewind every env to a snapshot of this env (or of one of the same kind, n_envs and ship count)."""
-        self.sim.restore(snap)
+    def restore(self, snap, weather=False):
+        """Rewind every env to a snapshot of this env (or of one of the same kind, n_envs and ship count);
+        weather=True: and to the weather the Snapshot carries."""
+        self.sim.restore(snap, weather=weather)
 
     def fork(self, src, source=None, weather="keep"):
         """Env i continues from the state of env src[i] — of this env as it is, or of the Snapshot `source`; an index
         outside [0, n_envs) leaves env i alone. weather="keep": a clone sails under the weather of the slot it lands
         in; "follow": the source envs' weather moves with their clones (through set_weather, a host-side setup
         call that needs the indices on the host and waits for the upload; without per-env weather there is nothing
-        to move). Weather is not part of a Snapshot: with a `source`, "follow" gathers the weather this env object
+        to move). "follow" does not read a Snapshot's weather: with a `source` it gathers the weather this env object
         has per slot now — not what was in force when the snapshot was taken, nor that of another env object it
         came from; a caller who archives snapshots keeps weather() beside them and calls set_weather itself.
+        "carry": the weather moves with the clones on the device (shipsim_weather_fork), without a host copy, a
+        synchronisation or an allocation, so that the fork can still be captured into a graph; with a `source` it is
+        the weather the Snapshot itself carries (snapshot(weather=True): what was in force when it was taken; a
+        Snapshot without is a ValueError). Without per-env weather there is nothing to move, as under "follow".
         Returns the device index tensor."""
-        if weather not in ("keep", "follow"):
-            raise ValueError(f"weather must be 'keep' or 'follow', not {weather!r}")
+        if weather not in ("keep", "follow", "carry"):
+            raise ValueError(f"weather must be 'keep', 'follow' or 'carry', not {weather!r}")
+        if weather == "carry":
+            carry = self.sim._weather_on
+            if carry and source is not None and getattr(source, "weather", None) is None:
+                raise ValueError("weather='carry': the source Snapshot carries no weather (snapshot(weather=True))")
+            return self.sim.fork(src, source=source, weather=carry)
         w = self.weather() if weather == "follow" else None
         s = self.sim.fork(src, source=source)
         if w is not None:
@@ -156,20 +167,23 @@ class BatchedMultiShipRLEnv:
         2) src is the identity and nothing moves. counter: (1,) int64 device tensor, read; the caller advances it.
         With weather="keep" (what the in-place arrangement is for: a survivor's weather never changes under it)
         nothing is copied to the host and the whole step can be captured into a graph; "follow" is fork()'s
-        host-side weather move."""
+        host-side weather move, and "carry" its move on the device: a clone takes its source's weather with it, and
+        the step stays one capturable graph (what keeps the weighted estimate unbiased under per-env weather)."""
         src, w, total, status = resample(weight, potential, seed, counter, arrangement="in_place")
         self.fork_stream_state(src, ep_idx, dec_idx, log_len)
         self.fork(src, weather=weather)
         return src, w, total, status
 
     # -- state archive (beyond the reference; shipsim.StateArchive) --
-    def archive(self, n_cells):
+    def archive(self, n_cells, weather=False):
         """A shipsim.StateArchive of n_cells cells: a store of env states of any size, of which update(cell, score,
         carry) overwrites single cells with the best env seen and load(cell_of_env, carry) starts any env from any
         cell — the cell store of Go-Explore, the node pool of a tree search. Weather stays with the slot, as under
-        fork(weather="keep"): an env loaded from a cell sails under the weather of the slot it lands in. The
-        caller's stream arrays (ep_idx, dec_idx, log_len, a policy counter, weights) go in `carry`."""
-        return self.sim.archive(n_cells)
+        fork(weather="keep"): an env loaded from a cell sails under the weather of the slot it lands in — unless
+        weather=True (per-env weather must be in force): then a cell keeps the weather of the env stored and an env
+        loaded from it takes that weather, on the device. The caller's stream arrays (ep_idx, dec_idx, log_len, a
+        policy counter, weights) go in `carry`."""
+        return self.sim.archive(n_cells, weather=weather)
 
     def relative_cells(self, bins, radius):
         """A Cartesian cell index per env, (n_envs,) int32 on the device, in [0, relative_cells_count(bins)): where

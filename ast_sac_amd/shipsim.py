@@ -92,11 +92,16 @@ def load_library(path=LIB_PATH):
                                                     C.c_int32, C.c_double, P, C.c_int64, P, P, P]),
                            ("shipsim_tree_expand", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P, P, C.c_int64,
                                                     P, P]),
-                           ("shipsim_tree_backup", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P, P])):
+                           ("shipsim_tree_backup", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P, P]),
+                           ("shipsim_weather_bytes", [C.c_int32]),
+                           ("shipsim_weather_store", [P, P, C.c_int64, C.c_int32, P]),
+                           ("shipsim_weather_load", [P, P, C.c_int64, C.c_int32, P]),
+                           ("shipsim_weather_fork", [P, P])):
         try:
             getattr(L, name).argtypes = argtypes
             if name in ("shipsim_state_bytes", "shipsim_resample_workspace_bytes", "shipsim_archive_bytes",
-                        "shipsim_archive_workspace_bytes", "shipsim_tree_bytes", "shipsim_tree_workspace_bytes"):
+                        "shipsim_archive_workspace_bytes", "shipsim_tree_bytes", "shipsim_tree_workspace_bytes",
+                        "shipsim_weather_bytes"):
                 getattr(L, name).restype = C.c_int64
         except AttributeError:
             if "SHIPSIM_LIB" not in os.environ:
@@ -125,21 +130,25 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_archive_workspace_bytes", "shipsim_archive_elect", "shipsim_set_stream_grouping",
                     "shipsim_get_stream_grouping", "shipsim_sbmpc_nominal", "shipsim_tree_bytes", "shipsim_tree_layout",
                     "shipsim_tree_workspace_bytes", "shipsim_tree_init", "shipsim_tree_select", "shipsim_tree_expand",
-                    "shipsim_tree_backup")
+                    "shipsim_tree_backup", "shipsim_weather_bytes", "shipsim_weather_store", "shipsim_weather_load",
+                    "shipsim_weather_fork")
 
 
 class Snapshot:
     """The complete dynamic state of every env of a handle (ShipSim.snapshot): `data`, a uint8 device tensor of
     state_bytes, and the shape it belongs to — kind, n_envs, n_ships — with the build string of the library that
-    wrote it (the layout of the bytes is that build's)."""
+    wrote it (the layout of the bytes is that build's). `weather`: None, or the per-env weather in force when it
+    was taken (snapshot(weather=True)), a (WEATHER_ROWS, n_envs) float64 device tensor (shipsim_weather_store)."""
 
-    __slots__ = ("data", "kind", "n_envs", "n_ships", "build")
+    __slots__ = ("data", "kind", "n_envs", "n_ships", "build", "weather")
 
-    def __init__(self, data, kind, n_envs, n_ships, build):
+    def __init__(self, data, kind, n_envs, n_ships, build, weather=None):
         self.data, self.kind, self.n_envs, self.n_ships, self.build = data, int(kind), int(n_envs), int(n_ships), build
+        self.weather = weather
 
     def clone(self):
-        return Snapshot(self.data.clone(), self.kind, self.n_envs, self.n_ships, self.build)
+        return Snapshot(self.data.clone(), self.kind, self.n_envs, self.n_ships, self.build,
+                        None if self.weather is None else self.weather.clone())
 
 
 class StateArchive:
@@ -149,14 +158,19 @@ class StateArchive:
     candidates the cell has had) and `carry`, the per-cell copies of the caller's per-env tensors — and the shape it
     belongs to: kind, n_ships and the build string of the library that laid it out. Any handle of that kind, ship
     count and build, whatever its n_envs, may store into it and load from it (`sim`; default: the handle it was
-    made by). Weather is not state: it stays with the slot, as under fork(weather="keep"). Every method is
+    made by). Weather is not state: it stays with the slot, as under fork(weather="keep") — unless the archive
+    was made with weather=True: then it owns `weather`, a zeroed (WEATHER_ROWS, n_cells) float64 tensor, and store,
+    load and update move the per-env weather of the handle (which must have it in force) by the same index arrays
+    they move the state with (shipsim_weather_store / _load). Every method is
     asynchronous on the current stream, without a host round trip or an allocation after the first call with the
     same carry keys, and can be captured into a graph."""
 
-    def __init__(self, sim, n_cells):
+    def __init__(self, sim, n_cells, weather=False):
         n_cells = int(n_cells)
         if not 1 <= n_cells <= abi.ARCHIVE_MAX_CELLS:
             raise ShipSimError(f"archive: n_cells must be in 1..{abi.ARCHIVE_MAX_CELLS}, not {n_cells}")
+        if weather and not sim._weather_on:
+            raise ShipSimError("archive: weather=True needs a handle with per-env weather in force (set_weather)")
         self.sim, self.n_cells, self.device = sim, n_cells, sim.device
         self.kind, self.n_ships, self.build = int(sim.cfg.kind), sim.n_ships, sim.L.shipsim_build_info().decode()
         nbytes = int(sim.L.shipsim_archive_bytes(sim.h, n_cells))
@@ -170,11 +184,12 @@ class StateArchive:
         self.env_of_cell = torch.full((n_cells,), -1, dtype=torch.int32, device=dev)
         self.n_improved = torch.zeros(1, dtype=torch.int32, device=dev)
         self.carry = {}
+        self.weather = torch.zeros((abi.WEATHER_ROWS, n_cells), dtype=torch.float64, device=dev) if weather else None
 
     def as_snapshot(self):
         """The archive's bytes as a Snapshot of n_cells envs (they share the memory): what restore() and
         fork(source=) of a handle of n_envs == n_cells take."""
-        return Snapshot(self.data, self.kind, self.n_cells, self.n_ships, self.build)
+        return Snapshot(self.data, self.kind, self.n_cells, self.n_ships, self.build, self.weather)
 
     def _handle(self, sim, what):
         sim = self.sim if sim is None else sim
@@ -187,6 +202,8 @@ class StateArchive:
             raise ShipSimError(f"{what}: the archive was laid out by another build ({self.build!r}, this is {build!r})")
         if sim.device != self.device:
             raise ShipSimError(f"{what}: the archive is on {self.device}, the handle on {sim.device}")
+        if self.weather is not None and not sim._weather_on:
+            raise ShipSimError(f"{what}: the archive carries weather, the handle has no per-env weather in force")
         return sim
 
     def _index(self, x, n, what):
@@ -203,6 +220,8 @@ class StateArchive:
         sim._follow_stream()
         sim._check(sim.L.shipsim_archive_store(sim.h, _ptr(self.data), self.data.numel(), self.n_cells, _ptr(idx)),
                    "shipsim_archive_store")
+        if self.weather is not None:
+            sim._weather_store(self.weather, idx)
         self._keep = idx
         return idx
 
@@ -218,6 +237,8 @@ class StateArchive:
         sim._follow_stream()
         sim._check(sim.L.shipsim_archive_load(sim.h, _ptr(self.data), self.data.numel(), self.n_cells, _ptr(idx)),
                    "shipsim_archive_load")
+        if self.weather is not None:
+            sim._weather_load(self.weather, idx)
         if carry:
             ok = (idx >= 0) & (idx < self.n_cells)
             at = idx.clamp(0, self.n_cells - 1).long()
@@ -483,22 +504,59 @@ class ShipSim:
             raise ShipSimError(f"shipsim_state_bytes failed ({n})")
         return n
 
-    def snapshot(self, out=None):
+    def snapshot(self, out=None, weather=False):
         """The complete state of every env, mid-decision state included, as a Snapshot on the device (asynchronous
         on the current stream). out: a Snapshot of this handle's shape to overwrite instead of allocating. The
-        stream arrays a caller owns (ep_idx, dec_idx, log_len, the policy's counter) are the caller's to keep."""
+        stream arrays a caller owns (ep_idx, dec_idx, log_len, the policy's counter) are the caller's to keep.
+        weather=True: the per-env weather in force goes into the Snapshot's `weather` too (shipsim_weather_store;
+        the handle must have per-env weather, and an `out` must hold a weather tensor already)."""
+        if weather:
+            self._need_weather("snapshot")
         if out is None:
             out = Snapshot(torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device), self.cfg.kind,
-                           self.n_envs, self.n_ships, self.L.shipsim_build_info().decode())
+                           self.n_envs, self.n_ships, self.L.shipsim_build_info().decode(),
+                           torch.empty((abi.WEATHER_ROWS, self.n_envs), dtype=torch.float64, device=self.device)
+                           if weather else None)
         else:
-            self._check_snapshot(out, "snapshot")
+            self._check_snapshot(out, "snapshot", weather)
         self._follow_stream()
         self._check(self.L.shipsim_snapshot(self.h, _ptr(out.data), out.data.numel()), "shipsim_snapshot")
+        if weather:
+            self._weather_store(out.weather, None)
         return out
 
-    def _check_snapshot(self, snap, what):
+    # weather that moves with the state (include/shipsim.h: shipsim_weather_store)
+    def _need_weather(self, what):
+        if not self._weather_on:
+            raise ShipSimError(f"{what}: weather=True needs per-env weather in force on the handle (set_weather)")
+
+    def _weather_buffer(self, wx, what):
+        if wx is None:
+            raise ShipSimError(f"{what}: the source carries no weather (it was taken without weather=True)")
+        if wx.dtype != torch.float64 or wx.device != self.device or not wx.is_contiguous() or wx.dim() != 2 \
+                or wx.shape[0] != abi.WEATHER_ROWS:
+            raise ShipSimError(f"{what}: weather must be a contiguous ({abi.WEATHER_ROWS}, n) float64 tensor on "
+                               f"{self.device}")
+        return wx
+
+    def _weather_store(self, wx, index):
+        wx = self._weather_buffer(wx, "weather store")
+        self._check(self.L.shipsim_weather_store(self.h, _ptr(wx), wx.numel() * 8, wx.shape[1], _ptr(index)),
+                    "shipsim_weather_store")
+
+    def _weather_load(self, wx, index):
+        wx = self._weather_buffer(wx, "weather load")
+        self._check(self.L.shipsim_weather_load(self.h, _ptr(wx), wx.numel() * 8, wx.shape[1], _ptr(index)),
+                    "shipsim_weather_load")
+
+    def _check_snapshot(self, snap, what, weather=False):
         if not isinstance(snap, Snapshot):
             raise ShipSimError(f"{what}: expected a Snapshot, got {type(snap).__name__}")
+        if weather:
+            self._need_weather(what)
+            w = self._weather_buffer(snap.weather, what)
+            if w.shape[1] != snap.n_envs:
+                raise ShipSimError(f"{what}: the snapshot's weather has {w.shape[1]} slots, its state {snap.n_envs}")
         mine = (int(self.cfg.kind), self.n_envs, self.n_ships)
         if (snap.kind, snap.n_envs, snap.n_ships) != mine:
             raise ShipSimError(f"{what}: the snapshot is of (kind, n_envs, n_ships) = "
@@ -511,28 +569,40 @@ class ShipSim:
             raise ShipSimError(f"{what}: the snapshot's data must be a contiguous uint8 tensor of {self.state_bytes} "
                                f"bytes on {self.device}")
 
-    def restore(self, snap):
+    def restore(self, snap, weather=False):
         """Put a Snapshot back (shipsim_restore): from the next launch on the handle continues, bit for bit, as it
         did after the snapshot was taken, given the caller's own stream arrays as they were. A Snapshot of another
-        kind, n_envs, ship count or build is refused before the library is called."""
-        self._check_snapshot(snap, "restore")
+        kind, n_envs, ship count or build is refused before the library is called. weather=True: the weather the
+        Snapshot carries goes back too (shipsim_weather_load); one without, or a handle without per-env weather,
+        is refused before the library is called."""
+        self._check_snapshot(snap, "restore", weather)
         self._follow_stream()
         self._check(self.L.shipsim_restore(self.h, _ptr(snap.data), snap.data.numel()), "shipsim_restore")
+        if weather:
+            self._weather_load(snap.weather, None)
 
-    def fork(self, src, source=None):
+    def fork(self, src, source=None, weather=False):
         """Env i takes the state of env src[i] (shipsim_fork): of this handle as it is (source None), or of a
         Snapshot. src: (n_envs,) device int32 tensor or anything torch.as_tensor takes; any index array is served
         (permutations, broadcasts, cycles), and an index outside [0, n_envs) leaves env i as it is. A clone runs
-        under its new slot's weather, noise and actions; one paused mid-decision resumes without consuming an
-        action. Returns the index tensor used."""
+        under its new slot's noise and actions, and under its new slot's weather unless weather=True: then env i
+        also takes the per-env weather of env src[i] (shipsim_weather_fork), or of slot src[i] of the Snapshot's own
+        weather (shipsim_weather_load), on the device and capturable like the fork itself. One paused mid-decision
+        resumes without consuming an action. Returns the index tensor used."""
         s = self._dev(src, torch.int32).reshape(-1)
         if s.numel() != self.n_envs:
             raise ShipSimError(f"fork: src has {s.numel()} entries, expected {self.n_envs}")
         if source is not None:
-            self._check_snapshot(source, "fork")
+            self._check_snapshot(source, "fork", weather)
+        elif weather:
+            self._need_weather("fork")
         self._follow_stream()
         self._check(self.L.shipsim_fork(self.h, _ptr(source.data) if source is not None else None, self.state_bytes,
                                         _ptr(s)), "shipsim_fork")
+        if weather and source is not None:
+            self._weather_load(source.weather, s)
+        elif weather:
+            self._check(self.L.shipsim_weather_fork(self.h, _ptr(s)), "shipsim_weather_fork")
         self._keep_fork = s
         return s
 
@@ -548,10 +618,12 @@ class ShipSim:
         self._check(self.L.shipsim_level_distance(self.h, _ptr(out)), "shipsim_level_distance")
         return out
 
-    def archive(self, n_cells):
+    def archive(self, n_cells, weather=False):
         """A StateArchive of n_cells cells for handles of this one's kind and ship count (include/shipsim.h:
-        shipsim_archive_store): zeroed, every cell empty. Allocates; call it outside graph capture."""
-        return StateArchive(self, n_cells)
+        shipsim_archive_store): zeroed, every cell empty. weather=True: it also keeps, per cell, the per-env weather
+        of the env stored (this handle must have per-env weather in force). Allocates; call it outside graph
+        capture."""
+        return StateArchive(self, n_cells, weather=weather)
 
     # -- per-env weather (include/shipsim.h: shipsim_set_weather) --
     WEATHER_KEYS = ("wind_speed", "wind_direction", "current_north", "current_east")
@@ -583,10 +655,13 @@ class ShipSim:
         self.lanes_per_env = int(self.L.shipsim_lanes_per_env(self.h))
 
     def weather(self):
-        """dict of four float64 arrays of n_envs (WEATHER_KEYS) as set by set_weather; None when uniform."""
+        """dict of four float64 arrays of n_envs (WEATHER_KEYS): what set_weather set, moved as fork, restore and an
+        archive's load have moved it since (then read back from the device, after a wait for the handle's stream);
+        None when uniform."""
         if not self._weather_on:
             return None
         out = [np.empty(self.n_envs, dtype=np.float64) for _ in self.WEATHER_KEYS]
+        self._follow_stream()  # (the stream a readback waits for)
         self._check(self.L.shipsim_get_weather(self.h, *[C.c_void_p(a.ctypes.data) for a in out]),
                     "shipsim_get_weather")
         return dict(zip(self.WEATHER_KEYS, out))

@@ -98,6 +98,10 @@ TE_FLAG_COLLISION, TE_FLAG_IMMINENT = 1, 2
 SBMPC_IN = 17
 SBMPC_MULTI_IN = 10 + 7 * MAX_OBS  # shipsim_sbmpc_eval_multi rows (include/shipsim.h)
 ARCHIVE_MAX_CELLS = 1 << 22  # SHIPSIM_ARCHIVE_MAX_CELLS: the most cells of a state archive
+# the rows of a weather buffer (shipsim_weather_store; csrc/shipsim_weather_host.hpp): n_slots doubles each
+WEATHER_ROWS = 6
+(WEATHER_ROW_WIND_SPEED, WEATHER_ROW_WIND_SIN, WEATHER_ROW_WIND_COS, WEATHER_ROW_CURRENT_NORTH,
+ WEATHER_ROW_CURRENT_EAST, WEATHER_ROW_WIND_DIRECTION) = range(6)
 TREE_MAX_CHILDREN = 64  # SHIPSIM_TREE_MAX_CHILDREN: the most children of a search-tree node
 TREE_MAX_DEPTH = 32  # SHIPSIM_TREE_MAX_DEPTH
 TREE_MAX_WORKERS = 1 << 22  # SHIPSIM_TREE_MAX_WORKERS: the most workers of one select / expand / backup

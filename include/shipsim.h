@@ -337,7 +337,8 @@ int shipsim_set_state(shipsim_handle* h, int32_t field, const void* src);
  * All three are asynchronous on the handle's stream, without host synchronisation or host allocation (but for
  * the staging block's allocation), and may be captured into a graph once the staging block exists.
  * Not state, staying with the handle and the slot: the config, per-env weather, the stream tail, lanes per env, the
- * non-finite counter, trajectory buffers. So a clone sails under the weather of the slot it lands in; under a
+ * non-finite counter, trajectory buffers. So a clone sails under the weather of the slot it lands in, unless the
+ * caller moves the weather with it (shipsim_weather_fork / _store / _load, by the same index array); under a
  * stochastic policy it draws its slot's noise (Philox is keyed by env index), which is what splitting wants; an env
  * cloned while paused mid-decision resumes without consuming an action, one cloned while awaiting a decision
  * consumes its new slot's action. A snapshot may go into another handle of the same kind, n_envs and ship count,
@@ -417,7 +418,8 @@ int shipsim_level_distance(shipsim_handle* h, double* out);
  * be captured into a graph. The index is tested before any address is formed from it; the loads are gathered and
  * the stores consecutive, so duplicate indices are harmless and no state can be torn. All kinds that shipsim_fork
  * serves (AST with K = 1..4, NONIW, SINGLE); what is not state (weather, the config, the stream tail) stays with the
- * slot, as under shipsim_fork, and the arrays the caller owns (ep_idx, dec_idx, log_len) are the caller's to keep
+ * slot, as under shipsim_fork (per-env weather goes into a weather buffer of n_cells slots beside the archive:
+ * shipsim_weather_store / _load with the same index arrays), and the arrays the caller owns (ep_idx, dec_idx, log_len) are the caller's to keep
  * per cell. SHIPSIM_EINVAL with the reason in shipsim_last_error: a NULL archive or index array; n_cells < 1 or
  * above SHIPSIM_ARCHIVE_MAX_CELLS; bytes != shipsim_archive_bytes(h, n_cells); an archive not 16-byte aligned; a
  * handle with trajectory recording enabled.
@@ -692,7 +694,8 @@ int shipsim_get_stream_grouping(shipsim_handle* h, int32_t* slot_env_out);
  * current_velocity_component_from_north / _from_east). shipsim_set_weather gives every env its own: four HOST
  * arrays of n_envs doubles (m/s, rad, m/s, m/s) — a setup call like the config, not a per-step one. The library
  * takes sin and cos of the direction on the host (the libm calls shipsim_create makes for the config's direction),
- * copies the arrays, uploads on the handle's stream and waits for the upload: do not call it during graph capture.
+ * copies the arrays, uploads on the handle's stream and waits for the upload: do not call it during graph capture
+ * (the first call also allocates the device table and the staging table of shipsim_weather_fork).
  * From the next launch on shipsim_reset, shipsim_step, shipsim_run_table and shipsim_run_policy (in-kernel resets
  * included) run env i under its values, with the results, bit for bit, of a uniform handle whose config carries
  * them. The values persist across resets until set again.
@@ -711,6 +714,42 @@ int shipsim_set_weather(shipsim_handle* h, const double* wind_speed, const doubl
                         const double* current_from_north, const double* current_from_east);
 int shipsim_get_weather(shipsim_handle* h, double* wind_speed, double* wind_direction,
                         double* current_from_north, double* current_from_east);
+
+/* ---- per-env weather that moves with the state: store, load, fork (additive to ABI 12) ----------------------
+ * Weather is not part of the state block, so shipsim_fork, shipsim_restore and shipsim_archive_load leave every slot's
+ * weather where it is. These calls move it, by the index arrays those calls take, so that a clone goes on under the
+ * weather that shaped its past. The handle's weather table on the device is six rows of n_envs doubles: wind speed,
+ * sin and cos of the wind direction (what the kernels read), current from north, current from east, and the wind
+ * direction as set (which its sin and cos do not give back bit for bit). A weather buffer is a caller-owned device
+ * buffer, 16-byte aligned, of six such rows of n_slots doubles, row r at byte r * n_slots * 8:
+ * shipsim_weather_bytes(n_slots) bytes (SHIPSIM_EINVAL outside 1..SHIPSIM_ARCHIVE_MAX_CELLS); with n_slots == n_envs
+ * it is byte for byte the handle's table.
+ *   shipsim_weather_store  slot c takes the weather of env env_of_slot[c] (n_slots int32 on the device). NULL: the
+ *                          identity, n_slots == n_envs only — a weather snapshot.
+ *   shipsim_weather_load   env i takes the weather of slot slot_of_env[i] (n_envs int32 on the device), written
+ *                          straight into the handle's table. NULL: the identity, n_slots == n_envs only — a restore;
+ *                          with n_slots == n_envs and an index, a fork from a snapshot. Values are not validated: a
+ *                          buffer holds what shipsim_weather_store wrote, and loading a slot never stored is the
+ *                          caller's error as loading an empty cell of a state archive is (defined, no fault).
+ *   shipsim_weather_fork   env i takes the weather env src_env[i] had before the call (n_envs int32 on the device;
+ *                          NULL: the identity): gathered into a library-owned staging table and copied back, one
+ *                          launch and one copy, as shipsim_fork does with the state.
+ * An index that names no slot of the source leaves the destination slot as it is; the kernel tests the index before
+ * it forms an address from it, its loads are gathered and its stores consecutive, and there are no atomics, so
+ * duplicate indices are harmless. All are asynchronous on the handle's stream, without host synchronisation or
+ * allocation (shipsim_set_weather allocated the table and the staging table), and may be captured into a graph from
+ * the first call on; the table never moves, so captured env launches stay valid.
+ * shipsim_get_weather follows: once one of the three has been called on a handle (during a capture too — a replay
+ * moves weather without a host call), it waits for the handle's stream and reads the four arrays back from the
+ * device table. On a handle that never called one it returns the host copy of what was set, as before.
+ * SHIPSIM_EINVAL with the reason in shipsim_last_error: a handle without per-env weather in force; a NULL buffer;
+ * n_slots outside 1..SHIPSIM_ARCHIVE_MAX_CELLS; bytes != shipsim_weather_bytes(n_slots); a buffer not 16-byte
+ * aligned; a NULL index with n_slots != n_envs. */
+int64_t shipsim_weather_bytes(int32_t n_slots);
+int shipsim_weather_store(shipsim_handle* h, void* wx, int64_t bytes, int32_t n_slots, const int32_t* env_of_slot);
+int shipsim_weather_load(shipsim_handle* h, const void* wx, int64_t bytes, int32_t n_slots,
+                         const int32_t* slot_of_env);
+int shipsim_weather_fork(shipsim_handle* h, const int32_t* src_env);
 
 /* ---- legacy per-tick MultiShipEnv (rl_env/ship_in_transit/env.py:783-1181) ----
  * AST kind. Each of the k ticks is one MultiShipEnv.step() (:1104-1173) of every env: test_step

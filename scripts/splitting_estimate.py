@@ -15,7 +15,15 @@ episode 0 ended in a collision over those whose episode 0 ended (the episodes af
 which favours the short ones, so they are counted but not used). Both are repeated --reps times with other seeds; means and sample standard deviations are written to
 profiles/splitting_estimate.json. Reported, not asserted: nobody has measured this scenario's collision probability.
 
+With one of the runner's four weather range flags every env sails under its own wind and current (weather.
+sample_weather, drawn once with --weather_seed and set again before every leg), and --weather says what a clone does
+about it: "carry" (the default then) takes its source's weather along on the device, which is the process the weights
+are unbiased for — weather has shaped the clone's whole past; "keep" leaves a clone under the weather of the slot it
+lands in, a process that changes weather mid-episode. The output then goes to profiles/splitting_estimate_weather.json.
+
     python scripts/splitting_estimate.py [--out FILE] [--envs N] [--reps R] [--ticks T] [--lambda METRES]
+        [--wind_speed_range LO HI] [--wind_direction_range LO HI] [--current_speed_range LO HI]
+        [--current_direction_range LO HI] [--weather_seed S] [--weather {keep,carry}]
 """
 import argparse
 import json
@@ -30,6 +38,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from ast_sac_amd import shipsim, shipsim_abi as abi  # noqa: E402
 from ast_sac_amd.rl_env.ship_in_transit.env import BatchedMultiShipRLEnv, default_args  # noqa: E402
+from ast_sac_amd.rl_env.ship_in_transit.weather import sample_weather  # noqa: E402
+
+# the runner's four range flags -> sample_weather's keyword arguments
+WEATHER_RANGE_FLAGS = (("wind_speed_range", "wind_speed", "m/s"), ("wind_direction_range", "wind_direction_deg", "degrees"),
+                       ("current_speed_range", "current_speed", "m/s"),
+                       ("current_direction_range", "current_direction_deg", "degrees"))
 
 CAP = 32   # decision records per env and launch
 N_EPS = 2  # table rows (a retired env reads row ep % 2 until its slot is refilled)
@@ -51,8 +65,10 @@ def _ended(log, ln, n_dec, row):
     return done | last, coll, (ln - ln.clamp(max=CAP)).sum()
 
 
-def run(env, ticks, lam, seed, split, launches=None, max_launches=512):
+def run(env, ticks, lam, seed, split, launches=None, max_launches=512, weather=None, weather_mode="keep"):
     dev, n, sim = env.device, env.n_envs, env.sim
+    if weather is not None:  # every leg starts from the weather as drawn: a leg under "carry" has moved it
+        env.set_weather(weather)
     n_dec = int(env.cfg.max_sampling_frequency)
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
@@ -92,7 +108,7 @@ def run(env, ticks, lam, seed, split, launches=None, max_launches=512):
         if not bool((weight > 0).any()):  # the loop's only look at the device: is anybody live
             break
         potential = torch.exp(-sim.level_distance() / lam)
-        src, weight, _, _ = env.split(weight, potential, seed, counter, ep, dec)
+        src, weight, _, _ = env.split(weight, potential, seed, counter, ep, dec, weather=weather_mode)
         counter += 1
         moved = src != own
         refilled += moved.sum()
@@ -113,7 +129,8 @@ def _mean_std(xs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "splitting_estimate.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/splitting_estimate.json, or with a weather range "
+                    "flag profiles/splitting_estimate_weather.json")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--ticks", type=int, default=256)
@@ -121,16 +138,34 @@ def main():
     ap.add_argument("--collav", default="sbmpc", choices=("sbmpc", "simple", "none"),
                     help="the own ship's collision avoidance (sbmpc: the scenario of record)")
     ap.add_argument("--seed", type=int, default=20251015, help="repetition r uses seed + 2 r and seed + 2 r + 1")
+    for flag, _, unit in WEATHER_RANGE_FLAGS:
+        ap.add_argument("--" + flag, type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                        help=f"every env draws its own value, uniform in [LO, HI] {unit}")
+    ap.add_argument("--weather_seed", type=int, default=0, metavar="S", help="env i draws its weather from PCG64(S + i)")
+    ap.add_argument("--weather", default=None, choices=("keep", "carry"),
+                    help="what a clone does about per-env weather (default with a range flag: carry)")
     args = ap.parse_args()
+    ranges = {kw: tuple(getattr(args, flag)) for flag, kw, _ in WEATHER_RANGE_FLAGS if getattr(args, flag) is not None}
+    if args.weather is not None and not ranges:
+        ap.error("--weather needs one of the weather range flags")
     if not torch.cuda.is_available():
         raise SystemExit("splitting_estimate.py needs a HIP device")
     dev = torch.device("cuda", 0)
     env = BatchedMultiShipRLEnv(default_args(collav_mode=args.collav), args.envs, device=dev)
+    weather, mode = None, "keep"
+    if ranges:
+        weather = sample_weather(args.envs, seed=args.weather_seed, cfg=env.cfg, **ranges)
+        mode = args.weather or "carry"
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "splitting_estimate_weather.json")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "splitting_estimate.json")
     legs = dict(splitting=[], plain=[])
     t0 = time.perf_counter()
     for rep in range(args.reps):
-        s = run(env, args.ticks, args.lam, args.seed + 2 * rep, True)
-        p = run(env, args.ticks, args.lam, args.seed + 2 * rep + 1, False, launches=s["launches"])  # the same budget
+        s = run(env, args.ticks, args.lam, args.seed + 2 * rep, True, weather=weather, weather_mode=mode)
+        p = run(env, args.ticks, args.lam, args.seed + 2 * rep + 1, False, launches=s["launches"],  # the same budget
+                weather=weather)
         legs["splitting"].append(s)
         legs["plain"].append(p)
         print(f"[estimate] rep {rep}: splitting {s['estimate']:.3e} ({s['launches']} launches, "
@@ -142,6 +177,8 @@ def main():
                reps=args.reps, seed=args.seed, device=torch.cuda.get_device_name(dev),
                build=shipsim.load_library().shipsim_build_info().decode(), seconds=dt,
                note="reported, not asserted: the scenario's collision probability has not been measured otherwise",
+               **({} if weather is None else dict(weather=dict(mode=mode, seed=args.weather_seed,
+                                                               ranges={k: list(v) for k, v in ranges.items()}))),
                splitting=dict(_mean_std([x["estimate"] for x in legs["splitting"]]), legs=legs["splitting"]),
                plain=dict(_mean_std([x["estimate"] for x in legs["plain"]]), legs=legs["plain"]))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
