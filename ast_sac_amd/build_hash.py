@@ -18,7 +18,7 @@ SOURCES = {
                 "ast_sac_amd/csrc/shipsim_archive.hip", "ast_sac_amd/csrc/shipsim_archive_host.hpp",
                 "ast_sac_amd/csrc/shipsim_grouping_host.hpp", "ast_sac_amd/csrc/shipsim_sbmpc_nominal.hpp",
                 "ast_sac_amd/csrc/shipsim_tree.hip", "ast_sac_amd/csrc/shipsim_tree_host.hpp",
-                "ast_sac_amd/csrc/shipsim_weather.hip"],
+                "ast_sac_amd/csrc/shipsim_weather.hip", "ast_sac_amd/csrc/shipsim_tickmath.hpp"],
     "sacfused": ["ast_sac_amd/csrc/sac_kernels.hip", "include/sac_fused.h"],
 }
 

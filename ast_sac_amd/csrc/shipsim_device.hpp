@@ -20,6 +20,7 @@
 #include "shipsim.h"
 #include "shipsim_diag.hpp"
 #include "shipsim_types.hpp"  // ShipConst, Params, Edge, PolyBox, py_min / py_max, poly_contains, map_inside
+#include "shipsim_tickmath.hpp"  // tm_sincos, tm_atan, tm_exp and their table
 
 namespace shipsim {
 
@@ -188,6 +189,89 @@ __device__ __forceinline__ double pair_swap(double x) {
   return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ int pair_swap_i(int x) { return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, false); }
+
+// ---------------------------------------------------------------------------------------------
+// The tick's math-library calls (shipsim_tickmath.hpp): sincos of the heading, the LOS atan, the reward's exp
+// ---------------------------------------------------------------------------------------------
+// The table of shipsim_tickmath.hpp in registers, an entry delivered by one row broadcast (v_mov_b64_dpp
+// row_newbcast) instead of the two literal moves a double costs: an env is one 16-lane row, and lane l of a pair
+// holds one entry. The sincos and atan entries (0 .. kExp0 - 1) sit on the row's even lanes, eight to a pair: the
+// test ship's lanes, which are active wherever a ship ticks (a frozen obstacle ship's lanes sit that part out, and
+// a broadcast from a disabled lane does not deliver the entry). The exp entries sit on all sixteen lanes of the
+// last pair: the reward is formed where the env's whole row is active.
+struct TmRow {
+  static constexpr int kEvenPairs = (tickmath::kExp0 + 7) / 8, kPairs = kEvenPairs + 1;
+  static_assert(tickmath::kCount - tickmath::kExp0 <= 16, "the exp entries fit one row");
+  double t[kPairs];
+  __device__ __forceinline__ void load(int lane_in_row) {
+#pragma unroll
+    for (int p = 0; p < kEvenPairs; ++p) {
+      const int i = p * 8 + (lane_in_row >> 1);
+      t[p] = tickmath::tm_entry(i < tickmath::kExp0 ? i : -1);
+    }
+    t[kEvenPairs] = tickmath::tm_entry(tickmath::kExp0 + lane_in_row);
+  }
+  // entry I by a plain broadcast: the ten entries with no dead value at hand (the reductions' constants, atan's π/2
+  // pieces, the third coefficient of atan's and exp's chains). A sincos or atan entry is read from an even lane of the row, so inside the
+  // partial-row region its source is a test ship's lane, which is active there; a row's odd lanes are never a source
+  template <int I>
+  __device__ __forceinline__ double k() const {
+    static_assert(I >= 0 && I < tickmath::kCount, "tickmath table index");
+    constexpr int pair = I < tickmath::kExp0 ? I / 8 : kEvenPairs;
+    constexpr int lane = I < tickmath::kExp0 ? 2 * (I % 8) : I - tickmath::kExp0;
+    return __builtin_amdgcn_mov_dpp(t[pair], kDppRowBcast + lane, 0xF, 0xF, true);
+  }
+  // entry I delivered into the register of `dead` (the provider interface of shipsim_tickmath.hpp: a value that is
+  // not read again). The broadcast names `dead` as what a lane without a source would keep — no lane is without one,
+  // the source lanes being chosen as above — so it cannot be issued before `dead`'s last use and stays next to its own
+  // use, instead of at the top of the block with its result held until then
+  template <int I>
+  __device__ __forceinline__ double kd(double dead) const {
+    static_assert(I >= 0 && I < tickmath::kCount, "tickmath table index");
+    constexpr int pair = I < tickmath::kExp0 ? I / 8 : kEvenPairs;
+    constexpr int lane = I < tickmath::kExp0 ? 2 * (I % 8) : I - tickmath::kExp0;
+    return __builtin_amdgcn_update_dpp(dead, t[pair], kDppRowBcast + lane, 0xF, 0xF, false);
+  }
+};
+
+// The three calls as a tick makes them. BITS (SHIPSIM_TICK_MATH): 0 the device library's functions; 1 atan and exp
+// restated (tm_atan, tm_exp: the library's operations, inlined); 2 sincos as the restated small-argument path under
+// one guard, the library's call on the other side; 4 the constants by row broadcast (TmRow) instead of literals.
+// With the broadcast the sincos guard is taken per env row (row_lane0: the row's first lane in the wave): were a
+// ship alone to leave for the library's side, the lanes left behind would read their constants from its disabled
+// lanes.
+template <int BITS>
+struct TickMath {
+  TmRow row;
+  int row_lane0;
+  __device__ __forceinline__ void sincos_yaw(double x, double* s, double* c) const {
+    if constexpr ((BITS & 2) == 0) {
+      sincos(x, s, c);
+    } else {
+      bool ok = tickmath::tm_sincos_small_ok(x);
+      if constexpr (BITS & 4) {
+        const uint64_t out = __ballot(!ok);  // (disabled lanes: 0)
+        ok = ((uint32_t)(out >> row_lane0) & 0xFFFFu) == 0u;
+      }
+      if (ok) {
+        if constexpr (BITS & 4) tickmath::tm_sincos(x, row, s, c);
+        else tickmath::tm_sincos(x, tickmath::TmLiteral(), s, c);
+      } else {
+        sincos(x, s, c);
+      }
+    }
+  }
+  __device__ __forceinline__ double atan_los(double x) const {
+    if constexpr (BITS & 4) return tickmath::tm_atan(x, row);
+    else if constexpr (BITS & 1) return tickmath::tm_atan(x, tickmath::TmLiteral());
+    else return atan(x);
+  }
+  __device__ __forceinline__ double exp_reward(double x) const {
+    if constexpr (BITS & 4) return tickmath::tm_exp(x, row);
+    else if constexpr (BITS & 1) return tickmath::tm_exp(x, tickmath::TmLiteral());
+    else return exp(x);
+  }
+};
 
 // ---------------------------------------------------------------------------------------------
 // ship model: ship_model.py BaseShipModel / ShipModelAST, run_colav SimpleShipModel

@@ -43,6 +43,12 @@
 #ifndef SHIPSIM_SB_NOMINAL
 #define SHIPSIM_SB_NOMINAL 3
 #endif
+// Steps of the headline streams' own evaluation of the tick's math-library calls (ast_step_kernel: TMB; TickMath,
+// shipsim_device.hpp), a bit per step the same way: 1 atan and exp restated, 2 sincos(yaw) as the restated
+// small-argument path under one guard, 4 the constants by row broadcast; 0 is the tick on the device library.
+#ifndef SHIPSIM_TICK_MATH
+#define SHIPSIM_TICK_MATH 7
+#endif
 
 using namespace shipsim;
 static_assert(kWeatherCols == weather_host::kCols && WX_WIND_SPEED == weather_host::kWindSpeed &&
@@ -72,13 +78,15 @@ struct Traj {
 // PRE: (pre_q, pre_e) = los_q at (s.n, s.e) on the current segment, evaluated earlier in the tick; used unless the
 // waypoint index advances here
 // PP: Params, or its register copy in the kernels that hold one (TickConstRegs)
-template <bool DETAILED, bool REC, bool PRE = false, class PP>
+// TM: how the course correction's atan is evaluated (TickMath; the device library's unless the caller says otherwise)
+template <bool DETAILED, bool REC, bool PRE = false, class PP, class TM = TickMath<0>>
 __device__ __forceinline__ void control_and_store(const ShipConst& c, const PP& P, Ship& s,
                                                   const double* __restrict__ rn, const double* __restrict__ re,
                                                   double offset, double speed_factor, double mach_dt,
                                                   int simple_collav_flag /*0 none, 1 rl(-15deg), 2 noniw(+15)*/,
                                                   bool imminent, double* row, double* fuel, double& ctrl_out,
-                                                  double& rudder_out, double pre_q = 0.0, double pre_e = 0.0) {
+                                                  double& rudder_out, double pre_q = 0.0, double pre_e = 0.0,
+                                                  const TM& tm = TM()) {
   const double N = s.n, E = s.e, H = s.yaw, U = s.u;
   double href;
   if constexpr (PRE) {
@@ -89,7 +97,7 @@ __device__ __forceinline__ void control_and_store(const ShipConst& c, const PP& 
       q = los_q(c, s, N, E, e_ct);
     }
     s.e_ct = e_ct;
-    href = s.seg_alpha + atan(los_windup(c, s, q));
+    href = s.seg_alpha + tm.atan_los(los_windup(c, s, q));
   } else {
     if (next_wpt_advance(c, s, N, E)) {
       s.next_wpt += 1;
@@ -165,19 +173,21 @@ __device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, con
   integrate(s, d, P.dt, mach_dt, DETAILED);
   sincos(s.yaw, &sy, &cy);
 }
-// the same with the tick's new position (n1, e1) formed by the caller before the control chain (early_pose)
-template <bool DETAILED, bool REC = false, bool PRE = false, class W = Params, class PP>
+// the same with the tick's new position (n1, e1) formed by the caller before the control chain (early_pose); TM: the
+// atan and the sincos as the caller's TickMath evaluates them
+template <bool DETAILED, bool REC = false, bool PRE = false, class W = Params, class PP, class TM = TickMath<0>>
 __device__ __forceinline__ void control_and_integrate_sc(const ShipConst& c, const PP& P, const W& wx, Ship& s,
                                                          const double* __restrict__ rn,
                                                          const double* __restrict__ re, double offset,
                                                          double speed_factor, double mach_dt, double n1, double e1,
-                                                         double& sy, double& cy, double pre_q, double pre_e) {
+                                                         double& sy, double& cy, double pre_q, double pre_e,
+                                                         const TM& tm = TM()) {
   double ctrl, rudder;
   control_and_store<DETAILED, REC, PRE>(c, P, s, rn, re, offset, speed_factor, mach_dt, 0, false, nullptr, nullptr, ctrl,
-                                        rudder, pre_q, pre_e);
+                                        rudder, pre_q, pre_e, tm);
   Deriv d = differentials_sc(c, wx, s, ctrl, rudder, DETAILED, sy, cy);
   integrate(s, d, n1, e1, P.dt, mach_dt, DETAILED);
-  sincos(s.yaw, &sy, &cy);
+  tm.sincos_yaw(s.yaw, &sy, &cy);
 }
 
 // store_last_simulation_data (ship_model.py:946-957) of a stopped ship: the previous row repeated
@@ -897,6 +907,14 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // step.)
   constexpr bool SB_NOM = LM_REQ && COLLAV == SHIPSIM_COLLAV_SBMPC && (SHIPSIM_SB_NOMINAL & 1);
   constexpr bool SB_NOM_ALG = SB_NOM && (SHIPSIM_SB_NOMINAL & 2);
+  // The headline of them, the table stream with collav sbmpc, evaluates the three math-library calls of the steady
+  // tick itself (TickMath, shipsim_device.hpp; shipsim_tickmath.hpp restates the library operation for operation, so
+  // the values are its bits): sincos(yaw) after the Euler step, the LOS course correction's atan and the reward's exp,
+  // with their fp64 constants delivered from a table in registers by one row broadcast each (DESIGN.md §9 "The
+  // tick's math"). The other three streams keep the library's calls and the assembly they had: with the table they
+  // lost (collav none −3.3 %, the policy stream −1.6 %). (SHIPSIM_TICK_MATH, at the top of the file: a bit per step.)
+  constexpr bool TM_KERNEL = FLAT && COLLAV == SHIPSIM_COLLAV_SBMPC && !POLICY;
+  constexpr int TMB = TM_KERNEL ? ((SHIPSIM_TICK_MATH & 4) ? 7 : (SHIPSIM_TICK_MATH & 3)) : 0;
   using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
   // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
   // instantiation compiles to the code it had (the dead arm of a constant condition is not emitted)
@@ -1232,6 +1250,9 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // global loads of a query are only issued when the cell changes (-2: none yet)
   int g_cell = -2, g_flag = GRID_MIXED;
   uint64_t g_mask = 0;
+  TickMath<TMB> tmath;
+  tmath.row_lane0 = env_lane0;
+  if constexpr (TMB & 4) tmath.row.load(lie);  // the table's entries on the env row's lanes, for the launch
   // (an int: OPQ kernels hold it in a VGPR, not as a lane mask live across the whole tick loop)
   int going = opaque_if<OPQ>((running && !ready && (budget <= 0 || ticks < budget)) ? 1 : 0);
   PT_DECL;
@@ -1472,8 +1493,10 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
           const LaneWeather wxr = {PT.vc_n, PT.vc_e, PT.wind_speed, PT.wind_sin, PT.wind_cos};
           static_assert(EARLY_MAP == RC_PAR, "the step and the new position were formed at the top of the ship tick");
           const TickStep pd = {ep_dt};
+          if constexpr (TMB & 4)  // (diagnostics build: the table's source lanes, the row's even ones, are active)
+            SHIPSIM_INDEX_CHECK(((__builtin_amdgcn_read_exec() >> env_lane0) & 0x5555u) == 0x5555u, 14);
           control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, pd, wxr, s, rn, re, -off, sf, mach_dt, ep_n, ep_e, sy, cy,
-                                                           los_pre_q, los_pre_e);
+                                                           los_pre_q, los_pre_e, tmath);
         } else {
           control_and_integrate_sc<DETAILED, REC, LOS_PRE>(c, P, weather_of(P, lw), s, rn, re, -off, sf, mach_dt,
                                                            (SIMPLE && is_test) ? 1 : 0, imminent,
@@ -1660,7 +1683,8 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
         else
           xj = (j == 0) ? xv[0] : (j == 1) ? xv[1] : (j == 2) ? xv[2] : (j == 3) ? xv[3] : xv[4];
         const RewardTerm to = lds_rterm[j];
-        const double ej = exp(div_by(-((xj - to.t) * (xj - to.t)), to.o, to.y));
+        if constexpr (TMB & 4) SHIPSIM_LANE_CHECK(LPE, 15);  // (the exp entries' source lanes: the whole row)
+        const double ej = tmath.exp_reward(div_by(-((xj - to.t) * (xj - to.t)), to.o, to.y));
         ex[0] = env_lane_d<LPE, reward_lane<SLOTS>(0)>(ej, env_lane0);
         ex[1] = env_lane_d<LPE, reward_lane<SLOTS>(1)>(ej, env_lane0);
         ex[2] = env_lane_d<LPE, reward_lane<SLOTS>(2)>(ej, env_lane0);
@@ -2261,6 +2285,40 @@ __global__ __launch_bounds__(64) void sbmpc_nominal_kernel(int n, double tf, dou
   const int n_samp = (int)(tf / dt);
   flag_out[i] = (sbmpc_nominal_holds(q, n_samp, dt).holds ? 1 : 0) |
                 (sbmpc_nominal_holds_seg(q, seg_sin, seg_cos, a, n_samp, dt).holds ? 2 : 0);
+}
+
+// The tick's three math-library calls over n arguments, one per lane (shipsim_tickmath_eval): the device library's
+// value, the restated form's with literal constants (TickMath<3>) and the row-broadcast form's (TickMath<7>), as the
+// headline streams call them. fn 0 sincos (sine, cosine), 1 atan, 2 exp (second value 0). Lanes past n evaluate the
+// last argument and write nothing, so every lane of a row is active at the broadcasts.
+__global__ __launch_bounds__(64) void tickmath_eval_kernel(int fn, int n, const double* __restrict__ x,
+                                                           double* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const double a = x[i < n ? i : n - 1];
+  const int lane = (int)(threadIdx.x & 63);
+  TickMath<3> lit;
+  lit.row_lane0 = lane & ~15;
+  TickMath<7> row;
+  row.row_lane0 = lane & ~15;
+  row.row.load(lane & 15);
+  double v[6] = {0, 0, 0, 0, 0, 0};
+  if (fn == 0) {
+    sincos(a, &v[0], &v[1]);
+    lit.sincos_yaw(a, &v[2], &v[3]);
+    row.sincos_yaw(a, &v[4], &v[5]);
+  } else if (fn == 1) {
+    v[0] = atan(a);
+    v[2] = lit.atan_los(a);
+    v[4] = row.atan_los(a);
+  } else {
+    v[0] = exp(a);
+    v[2] = lit.exp_reward(a);
+    v[4] = row.exp_reward(a);
+  }
+  if (i < n) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) out[(size_t)i * 6 + k] = v[k];
+  }
 }
 
 // SBMPC.get_optimal_ctrl_offset over a do_list of n_obs obstacles (sbmpc.py:113-185) for n independent requests
@@ -3255,6 +3313,13 @@ int shipsim_sbmpc_nominal(int32_t n, double tf, double dt, const double* in, int
   if (n == 0) return SHIPSIM_OK;
   hipLaunchKernelGGL(sbmpc_nominal_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, n, tf, dt, in,
                      flag_out);
+  return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
+}
+
+int shipsim_tickmath_eval(int32_t fn, int32_t n, const double* in, double* out, void* stream) {
+  if (fn < 0 || fn > 2 || n < 0 || (n > 0 && (!in || !out))) return SHIPSIM_EINVAL;
+  if (n == 0) return SHIPSIM_OK;
+  hipLaunchKernelGGL(tickmath_eval_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, fn, n, in, out);
   return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
 }
 

@@ -84,6 +84,7 @@ def load_library(path=LIB_PATH):
                            ("shipsim_set_stream_grouping", [P, C.c_int32]),
                            ("shipsim_get_stream_grouping", [P, P]),
                            ("shipsim_sbmpc_nominal", [C.c_int32, C.c_double, C.c_double, P, P, P]),
+                           ("shipsim_tickmath_eval", [C.c_int32, C.c_int32, P, P, P]),
                            ("shipsim_tree_bytes", [C.c_int32, C.c_int32]),
                            ("shipsim_tree_layout", [C.c_int32, C.c_int32, P]),
                            ("shipsim_tree_workspace_bytes", [C.c_int32, C.c_int32]),
@@ -131,7 +132,7 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_get_stream_grouping", "shipsim_sbmpc_nominal", "shipsim_tree_bytes", "shipsim_tree_layout",
                     "shipsim_tree_workspace_bytes", "shipsim_tree_init", "shipsim_tree_select", "shipsim_tree_expand",
                     "shipsim_tree_backup", "shipsim_weather_bytes", "shipsim_weather_store", "shipsim_weather_load",
-                    "shipsim_weather_fork")
+                    "shipsim_weather_fork", "shipsim_tickmath_eval")
 
 
 class Snapshot:
@@ -746,6 +747,24 @@ def sbmpc_nominal(requests, tf=1000.0, dt=20.0, device="cuda"):
                                  C.c_void_p(stream.cuda_stream))
     if rc:
         raise ShipSimError(f"shipsim_sbmpc_nominal failed ({rc})")
+    return out
+
+
+TICKMATH_FN = {"sincos": 0, "atan": 1, "exp": 2}
+
+
+def tickmath_eval(fn, x, device="cuda"):
+    """The steady tick's math-library call `fn` ("sincos", "atan", "exp") on the device for a batch of arguments ->
+    (n, 3, 2) float64 tensor: [:, 0] the device library's value, [:, 1] the restated form's (csrc/shipsim_tickmath.hpp,
+    literal constants), [:, 2] the row-broadcast form's the headline streams run; the last axis is (sine, cosine) for
+    sincos and (value, 0) otherwise (shipsim_tickmath_eval)."""
+    L = load_library()
+    a = torch.as_tensor(x, dtype=torch.float64, device=device).contiguous().reshape(-1)
+    out = torch.zeros((a.shape[0], 3, 2), dtype=torch.float64, device=a.device)
+    stream = torch.cuda.current_stream(a.device)
+    rc = L.shipsim_tickmath_eval(TICKMATH_FN[fn], int(a.shape[0]), _ptr(a), _ptr(out), C.c_void_p(stream.cuda_stream))
+    if rc:
+        raise ShipSimError(f"shipsim_tickmath_eval failed ({rc})")
     return out
 
 

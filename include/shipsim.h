@@ -590,6 +590,13 @@ int shipsim_sbmpc_eval(int32_t n, double tf, double dt, const double* in, double
  * within rounding of the decision. Device pointers (flag_out: n int32); stateless, asynchronous on `stream`. */
 int shipsim_sbmpc_nominal(int32_t n, double tf, double dt, const double* in, int32_t* flag_out, void* stream);
 
+/* The three math-library calls of the two-ship decision streams' steady tick, for n arguments (additive to ABI 12):
+ * fn 0 sincos, 1 atan, 2 exp. out: n x 6 doubles per argument — the device library's value, the restated form's
+ * (ast_sac_amd/csrc/shipsim_tickmath.hpp, constants as literals) and the form the headline kernel runs (the table
+ * stream with collav sbmpc at 16 lanes per env: constants by row broadcast), two doubles each: (sine, cosine) for fn 0, (value, 0) otherwise. The three agree bit for bit. Device
+ * pointers; stateless, asynchronous on `stream`. */
+int shipsim_tickmath_eval(int32_t fn, int32_t n, const double* in, double* out, void* stream);
+
 /* SBMPC.get_optimal_ctrl_offset (sbmpc.py:113-185) over a do_list of n_obs dynamic obstacles (1 <= n_obs <=
  * SHIPSIM_MAX_OBS; active when any of them is within D_INIT, per scenario the worst obstacle's cost, the least worst
  * scenario: :149-178) for n independent requests, stateless like shipsim_sbmpc_eval (ABI 10). in: n x
