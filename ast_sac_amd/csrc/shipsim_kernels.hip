@@ -907,13 +907,16 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   // step.)
   constexpr bool SB_NOM = LM_REQ && COLLAV == SHIPSIM_COLLAV_SBMPC && (SHIPSIM_SB_NOMINAL & 1);
   constexpr bool SB_NOM_ALG = SB_NOM && (SHIPSIM_SB_NOMINAL & 2);
-  // The headline of them, the table stream with collav sbmpc, evaluates the three math-library calls of the steady
-  // tick itself (TickMath, shipsim_device.hpp; shipsim_tickmath.hpp restates the library operation for operation, so
-  // the values are its bits): sincos(yaw) after the Euler step, the LOS course correction's atan and the reward's exp,
-  // with their fp64 constants delivered from a table in registers by one row broadcast each (DESIGN.md §9 "The
-  // tick's math"). The other three streams keep the library's calls and the assembly they had: with the table they
-  // lost (collav none −3.3 %, the policy stream −1.6 %). (SHIPSIM_TICK_MATH, at the top of the file: a bit per step.)
-  constexpr bool TM_KERNEL = FLAT && COLLAV == SHIPSIM_COLLAV_SBMPC && !POLICY;
+  // Three of them (the table streams, and the policy stream with collav sbmpc) evaluate the three math-library calls
+  // of the steady tick themselves (TickMath, shipsim_device.hpp; shipsim_tickmath.hpp restates the library operation
+  // for operation, so the values are its bits): sincos(yaw) after the Euler step, the LOS course correction's atan and
+  // the reward's exp, with their fp64 constants delivered from a table in registers by one row broadcast each
+  // (DESIGN.md §9 "The tick's math"). With the tick loop tested at its top only the headline kernel gained by the
+  // table (collav none −3.3 %, the policy stream −1.6 %: what the allocator moved to accumulator registers); tested
+  // at its bottom, collav none gains 1.4 % and the policy stream 2.5 % (§9 "The tick loop, bottom-tested"). The policy
+  // stream with collav none has no bench line of its own and keeps the library's calls. (SHIPSIM_TICK_MATH, at the
+  // top of the file: a bit per step.)
+  constexpr bool TM_KERNEL = FLAT && !(POLICY && COLLAV != SHIPSIM_COLLAV_SBMPC);
   constexpr int TMB = TM_KERNEL ? ((SHIPSIM_TICK_MATH & 4) ? 7 : (SHIPSIM_TICK_MATH & 3)) : 0;
   using flag_t = std::conditional_t<OPM, int, bool>;  // (OPM: an int in a VGPR, not a lane mask)
   // a flag read / set through the VGPR where OPM. Elsewhere the plain expression, so that every other
@@ -1258,8 +1261,17 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
   PT_DECL;
   // CHAIN: the tick loop hands over to the (rare) chaining code below whenever a decision of the
   // wave completes, so the loop body itself is the per-decision kernel's.
+  // The streams' loop is tested at its bottom (a guard, then the test after the body; one spelling of the condition
+  // for both): with the test in the header the exits to the chaining code leave from there, and the register
+  // allocator carried the whole loop-carried state (Ship, sy / cy, the travel tracker, the small ints) to the outer
+  // code's registers in the header and back in front of the going region, about 150 moves per wave-tick (DESIGN.md
+  // §9 "The tick loop, bottom-tested"). The body has no continue and no goto, and its breaks are a switch's, so the
+  // two forms run the same statements. shipsim_step's kernels keep the test at the top and the code they had.
+  constexpr bool TICK_ROT = CHAIN != 0;
+#define TICK_LOOP_ON (__any(opaque_if<OPQ>(going)) && !(CHAIN && __any(opaque_if<OPQ>(ready) && opaque_if<OPQ>(running))))
   for (;;) {
-  while (__any(opaque_if<OPQ>(going)) && !(CHAIN && __any(opaque_if<OPQ>(ready) && opaque_if<OPQ>(running)))) {
+  if (!TICK_ROT || TICK_LOOP_ON) for (;;) {
+    if (!TICK_ROT && !TICK_LOOP_ON) break;
     // this tick's constants: re-read (scalar loads, LDS) rather than kept in registers across ticks
     const StepArgs& A = step_args();
     const Params& P = A.P;
@@ -1809,7 +1821,9 @@ __global__ __launch_bounds__(64) void ast_step_kernel(const StepArgs A_arg) {
     }
     }  // (the flat tick's going region)
     PT_MARK(3);
+    if (TICK_ROT && !TICK_LOOP_ON) break;
   }
+#undef TICK_LOOP_ON
   if (!CHAIN) break;
   if (POLICY || (ready && running)) chain_next();  // (policy: wave-uniform, a no-op unless a decision completed)
   {
