@@ -366,6 +366,115 @@ __global__ __launch_bounds__(kThreads) void tr_backup_kernel(const TR::Tree T, i
   }
 }
 
+// ---- the forest: R roots in one pool (shipsim_tree_init_forest / _select_forest) ----
+//   tr_init_forest_kernel  [R / 256]   the header and root r per thread
+//   select_forest: as select, with two launches in the place of tr_clear_kernel and level 0 as wide as the roots
+//   tr_roots_tile_kernel   [R / 1024]  the sum, saturating at W, of a tile of root_workers (clamped to 0..W)
+//   tr_clear_forest_kernel [max_nodes / 1024]  stay = newc = 0; the level counts; root r as entry r of level
+//                                      0's frontier with a_r arrivals: the tiles before (saturating), then an exclusive
+//                                      saturating scan inside the tile
+// Every term of the prefix is in 0..W and every add saturates at W <= 2^22, so no int32 overflows whatever
+// root_workers holds, and the adds being associative, the scan's order does not show.
+__global__ __launch_bounds__(kThreads) void tr_init_forest_kernel(const TR::Tree T, int32_t n_roots) {
+  const int32_t r = (int32_t)(blockIdx.x * (uint32_t)kThreads + threadIdx.x);
+  if (r == 0) TR::init_forest_header(T, n_roots);
+  if (r < n_roots && r < T.M) TR::init_root(T, r);
+}
+
+// the saturating sum of v (0..W) over the block, in every thread (red: kWavesPerBlock ints of LDS)
+__device__ __forceinline__ int32_t block_sum_sat(int32_t v, int32_t W, int32_t* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = TR::sat_add(v, __shfl_xor(v, o, 64), W);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int32_t s = 0;
+#pragma unroll
+  for (int k = 0; k < kWavesPerBlock; ++k) s = TR::sat_add(s, red[k], W);
+  return s;
+}
+
+// the saturating sum of v (0..W) over the threads of the block before this one (red: kWavesPerBlock ints of LDS)
+__device__ __forceinline__ int32_t block_exclusive_sat(int32_t v, int32_t W, int32_t* red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int32_t y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc = TR::sat_add(y, inc, W);
+  }
+  __syncthreads();
+  if (lane == 63) red[wave] = inc;
+  __syncthreads();
+  int32_t before = 0;
+#pragma unroll
+  for (int k = 0; k < kWavesPerBlock; ++k)
+    if (k < wave) before = TR::sat_add(before, red[k], W);
+  const int32_t prev = __shfl_up(inc, 1, 64);  // (the inclusive sum of the lane before: saturating adds have no inverse)
+  return lane ? TR::sat_add(before, prev, W) : before;
+}
+
+// the roots this call serves: the same number in every kernel of the call
+__device__ __forceinline__ int32_t forest_roots(const TR::Tree& T, int32_t n_roots) {
+  return TR::root_count(n_roots, T.hdr[TR::kHdrRoots], TR::node_count(T.hdr[TR::kHdrNodes], T.M));
+}
+
+__global__ __launch_bounds__(kThreads) void tr_roots_tile_kernel(const TR::Tree T, int32_t n_workers, int32_t n_roots,
+                                                                 const int32_t* __restrict__ root_workers,
+                                                                 int32_t* __restrict__ tile_sum) {
+  __shared__ int32_t red[kWavesPerBlock];
+  const int32_t R = forest_roots(T, n_roots);  // (<= n_roots, the entries root_workers has)
+  const int32_t first = (int32_t)blockIdx.x * TR::kScanTile + (int32_t)threadIdx.x * kPerThread;
+  int32_t s = 0;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k)
+    if (first + k < R) s = TR::sat_add(s, TR::root_ask(root_workers[first + k], n_workers), n_workers);
+  s = block_sum_sat(s, n_workers, red);
+  if (threadIdx.x == 0 && blockIdx.x < (unsigned)TR::kMaxTiles) tile_sum[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void tr_clear_forest_kernel(const TR::Tree T, int32_t n_workers, int32_t n_roots,
+                                                                   const int32_t* __restrict__ root_workers,
+                                                                   const int32_t* __restrict__ tile_sum,
+                                                                   int32_t* __restrict__ stay, int32_t* __restrict__ newc,
+                                                                   int32_t* __restrict__ level_count,
+                                                                   int32_t* __restrict__ fnode, int32_t* __restrict__ fcnt) {
+  __shared__ int32_t red[kWavesPerBlock];
+  const uint32_t n = TR::node_count(T.hdr[TR::kHdrNodes], T.M);
+  const int32_t R = forest_roots(T, n_roots), W = n_workers;  // (R <= n_roots <= W: the frontier's entries)
+  const int32_t first = (int32_t)blockIdx.x * TR::kScanTile + (int32_t)threadIdx.x * kPerThread;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const uint32_t v = (uint32_t)(first + k);
+    if (v < (uint32_t)(TR::kMaxDepth + 2)) level_count[v] = v == 0 ? R : 0;
+    if (v < n) {
+      stay[v] = 0;
+      newc[v] = 0;
+    }
+  }
+  if ((int64_t)blockIdx.x * TR::kScanTile >= n_roots) return;  // (the whole block: a host argument)
+  const int32_t tiles = blockIdx.x < (unsigned)TR::kMaxTiles ? (int32_t)blockIdx.x : TR::kMaxTiles;
+  int32_t earlier = 0;
+  for (int32_t k = (int32_t)threadIdx.x; k < tiles; k += kThreads) earlier = TR::sat_add(earlier, TR::clamp_count(tile_sum[k], W), W);
+  earlier = block_sum_sat(earlier, W, red);  // (at most 16 rounds)
+  int32_t c[kPerThread];
+  int32_t s = 0;
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    c[k] = first + k < R ? root_workers[first + k] : 0;
+    s = TR::sat_add(s, TR::root_ask(c[k], W), W);
+  }
+  int32_t before = TR::sat_add(earlier, block_exclusive_sat(s, W, red), W);
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    if (first + k < R) {
+      fnode[first + k] = first + k;
+      fcnt[first + k] = TR::root_arrival(c[k], before, W);
+    }
+    before = TR::sat_add(before, TR::root_ask(c[k], W), W);
+  }
+}
+
 inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 }  // namespace
@@ -452,6 +561,49 @@ int shipsim_tree_backup(void* tree, int64_t tree_bytes, int32_t max_nodes, int32
   const TR::Tree T = TR::view(tree, max_nodes, max_children);
   hipLaunchKernelGGL(tr_backup_kernel, dim3(blocks_for(n_workers, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, T,
                      n_workers, node, value, terminal);
+  return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
+}
+
+int shipsim_tree_init_forest(void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children, int32_t n_roots,
+                             void* stream) {
+  if (!TR::forest_init_args_ok(tree, tree_bytes, max_nodes, max_children, n_roots)) return SHIPSIM_EINVAL;
+  hipLaunchKernelGGL(tr_init_forest_kernel, dim3(blocks_for(n_roots, kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
+                     TR::view(tree, max_nodes, max_children), n_roots);
+  return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
+}
+
+int shipsim_tree_select_forest(const void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children,
+                               int32_t n_workers, int32_t n_roots, const int32_t* root_workers, int32_t max_depth,
+                               int32_t wnum, int32_t wden, double c_explore, void* workspace, int64_t workspace_bytes,
+                               int32_t* leaf_out, int32_t* expand_out, void* stream) {
+  if (!TR::forest_select_args_ok(tree, tree_bytes, max_nodes, max_children, n_workers, n_roots, root_workers, max_depth,
+                                 wnum, wden, c_explore, workspace, workspace_bytes, leaf_out, expand_out))
+    return SHIPSIM_EINVAL;
+  const TR::Tree T = TR::view((void*)tree, max_nodes, max_children);  // (select writes nothing through it)
+  const TR::Workspace S = TR::ws_view(workspace, max_nodes, n_workers);
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 block(kThreads);
+  hipLaunchKernelGGL(tr_roots_tile_kernel, dim3(blocks_for(n_roots, TR::kScanTile)), block, 0, st, T, n_workers, n_roots,
+                     root_workers, S.tile_sum);
+  const int32_t clear_n = max_nodes > TR::kMaxDepth + 2 ? max_nodes : TR::kMaxDepth + 2;  // (n_roots <= max_nodes)
+  hipLaunchKernelGGL(tr_clear_forest_kernel, dim3(blocks_for(clear_n, TR::kScanTile)), block, 0, st, T, n_workers, n_roots,
+                     root_workers, S.tile_sum, S.stay, S.newc, S.level_count, S.fnode[0], S.fcnt[0]);
+  // level d holds at most min(W, max_nodes, R * C^d) nodes
+  const int64_t most = n_workers < max_nodes ? n_workers : max_nodes;
+  int64_t width = n_roots;
+  for (int d = 0; d <= max_depth; ++d) {
+    unsigned blocks = blocks_for(width, kWavesPerBlock);
+    if (blocks > (unsigned)kLevelMaxBlocks) blocks = kLevelMaxBlocks;
+    hipLaunchKernelGGL(tr_level_kernel, dim3(blocks), block, 0, st, T, d, max_depth, wnum, wden, c_explore, n_workers,
+                       S.fnode[d & 1], S.fcnt[d & 1], S.fnode[(d + 1) & 1], S.fcnt[(d + 1) & 1], S.level_count, S.stay,
+                       S.newc);
+    width = width * max_children < most ? width * max_children : most;
+  }
+  const dim3 tiles(blocks_for(max_nodes, TR::kScanTile));
+  hipLaunchKernelGGL(tr_tile_kernel<true>, tiles, block, 0, st, T, 0, S.stay, S.newc, S.tile_sum);
+  hipLaunchKernelGGL(tr_offset_kernel, tiles, block, 0, st, T, S.stay, S.newc, S.tile_sum, S.off);
+  hipLaunchKernelGGL(tr_leaf_kernel, dim3(blocks_for(n_workers, kThreads)), block, 0, st, T, n_workers, S.off, S.stay,
+                     S.newc, leaf_out, expand_out);
   return hipGetLastError() == hipSuccess ? SHIPSIM_OK : SHIPSIM_EHIP;
 }
 

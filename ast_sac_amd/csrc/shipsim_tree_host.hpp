@@ -374,4 +374,129 @@ inline void backup(const Tree& T, int32_t n_workers, const int32_t* node, const 
   }
 }
 
+// ---- the forest: R roots in one node pool (include/shipsim.h: shipsim_tree_init_forest / _select_forest) ----
+// The header's fourth int is n_roots (0, as shipsim_tree_init writes it, reads as 1). Roots are nodes 0..R-1: parent
+// -1, depth 0, action 0, no children. Everything under a root is a tree as above; expand and backup do not know roots.
+constexpr int kHdrRoots = 3;
+
+inline bool forest_init_args_ok(const void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children,
+                                int32_t n_roots) {
+  return tree_args_ok(tree, tree_bytes, max_nodes, max_children) && n_roots >= 1 && n_roots <= max_nodes;
+}
+// the level-0 frontier lives in the W-entry frontier arrays: n_roots <= n_workers
+inline bool forest_select_args_ok(const void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children,
+                                  int32_t n_workers, int32_t n_roots, const void* root_workers, int32_t max_depth,
+                                  int32_t wnum, int32_t wden, double c_explore, const void* workspace,
+                                  int64_t workspace_bytes, const void* leaf_out, const void* expand_out) {
+  if (!select_args_ok(tree, tree_bytes, max_nodes, max_children, n_workers, max_depth, wnum, wden, c_explore, workspace,
+                      workspace_bytes, leaf_out, expand_out))
+    return false;
+  return n_roots >= 1 && n_roots <= max_nodes && n_roots <= n_workers && root_workers;
+}
+
+// the roots a select serves: the caller's, the header's (0 reads as 1; a negative one as none) and the nodes there are
+TR_HD constexpr int32_t root_count(int32_t n_roots, int32_t hdr_roots, uint32_t n_nodes) {
+  const int32_t h = hdr_roots == 0 ? 1 : (hdr_roots < 0 ? 0 : hdr_roots);
+  const int32_t r = n_roots < h ? n_roots : h;
+  return r < 0 ? 0 : ((uint32_t)r < n_nodes ? r : (int32_t)n_nodes);
+}
+// a + b, at most W, for a and b in 0..W: associative, so any order of a scan gives the same prefix, and no int32
+// overflows whatever the array holds
+TR_HD constexpr int32_t sat_add(int32_t a, int32_t b, int32_t W) { return a >= W - b ? W : a + b; }
+// what root_workers[r] asks for, as the prefix sees it
+TR_HD constexpr int32_t root_ask(int32_t c, int32_t W) { return clamp_count(c, W); }
+// the arrivals of a root that asks for c when the roots before it asked for `before` (saturated at W): the roots are
+// served in id order until the W workers are used up
+TR_HD constexpr int32_t root_arrival(int32_t c, int32_t before, int32_t W) {
+  const int32_t ask = root_ask(c, W), left = W - clamp_count(before, W);
+  return ask < left ? ask : left;
+}
+
+TR_HD inline void init_root(const Tree& T, int32_t r) {
+  T.parent[r] = -1;
+  T.depth[r] = 0;
+  T.n_children[r] = 0;
+  T.visits[r] = 0;
+  T.value_sum[r] = 0;
+  T.action[r] = 0.0f;
+  T.flags[r] = 0;
+}
+TR_HD inline void init_forest_header(const Tree& T, int32_t n_roots) {
+  for (int i = 0; i < kHdrInts; ++i) T.hdr[i] = 0;
+  T.hdr[kHdrNodes] = n_roots;
+  T.hdr[kHdrRoots] = n_roots;
+}
+// shipsim_tree_init_forest on the host (1 <= n_roots <= max_nodes)
+inline void init_forest(const Tree& T, int32_t n_roots) {
+  init_forest_header(T, n_roots);
+  for (int32_t r = 0; r < n_roots; ++r) init_root(T, r);
+}
+
+// a_r for r in [0, n_roots): the saturating prefix rule (arrivals_out: n_roots entries)
+inline void root_arrivals(const int32_t* root_workers, int32_t n_roots, int32_t n_workers, int32_t* arrivals_out) {
+  int32_t before = 0;
+  for (int32_t r = 0; r < n_roots; ++r) {
+    arrivals_out[r] = root_arrival(root_workers[r], before, n_workers);
+    before = sat_add(before, root_ask(root_workers[r], n_workers), n_workers);
+  }
+}
+
+// shipsim_tree_select_forest on the host, in the stages of the launches: the tile sums of root_workers, the clear
+// with the roots as level 0's frontier, the levels, the scan, the leaves
+inline void select_forest(const Tree& T, int32_t n_workers, int32_t n_roots, const int32_t* root_workers,
+                          int32_t max_depth, int32_t wnum, int32_t wden, double c_explore, const Workspace& S,
+                          int32_t* leaf_out, int32_t* expand_out) {
+  const uint32_t n = node_count(T.hdr[kHdrNodes], T.M);
+  const int32_t R = root_count(n_roots, T.hdr[kHdrRoots], n), W = n_workers;
+  const int32_t tiles = (R + kScanTile - 1) / kScanTile;
+  for (int32_t b = 0; b < tiles; ++b) {
+    int32_t s = 0;
+    for (int32_t r = b * kScanTile; r < R && r < (b + 1) * kScanTile; ++r) s = sat_add(s, root_ask(root_workers[r], W), W);
+    S.tile_sum[b] = s;
+  }
+  for (uint32_t v = 0; v < n; ++v) S.stay[v] = S.newc[v] = 0;
+  for (int d = 0; d < kMaxDepth + 2; ++d) S.level_count[d] = 0;
+  S.level_count[0] = R;
+  for (int32_t b = 0; b < tiles; ++b) {
+    int32_t before = 0;
+    for (int32_t k = 0; k < b; ++k) before = sat_add(before, S.tile_sum[k], W);
+    for (int32_t r = b * kScanTile; r < R && r < (b + 1) * kScanTile; ++r) {
+      S.fnode[0][r] = r;
+      S.fcnt[0][r] = root_arrival(root_workers[r], before, W);
+      before = sat_add(before, root_ask(root_workers[r], W), W);
+    }
+  }
+  int32_t arrived[kMaxChildren];
+  for (int d = 0; d <= max_depth; ++d) {
+    const int32_t* fn = S.fnode[d & 1];
+    const int32_t* fc = S.fcnt[d & 1];
+    int32_t* nn = S.fnode[(d + 1) & 1];
+    int32_t* ncn = S.fcnt[(d + 1) & 1];
+    for (int32_t i = 0; i < S.level_count[d]; ++i) {
+      const int32_t v = fn[i];
+      route_node(T, n, v, fc[i], max_depth, wnum, wden, c_explore, &S.stay[v], &S.newc[v], arrived);
+      for (int l = 0; l < T.C; ++l)
+        if (arrived[l] > 0) {
+          const int32_t pos = S.level_count[d + 1]++;
+          nn[pos] = T.child[(int64_t)v * T.C + l];
+          ncn[pos] = arrived[l];
+        }
+    }
+  }
+  int32_t o = 0;
+  for (uint32_t v = 0; v < n; ++v) {
+    S.off[v] = o;
+    o += S.stay[v] + S.newc[v];
+  }
+  for (int32_t w = 0; w < n_workers; ++w) {
+    leaf_out[w] = -1;
+    expand_out[w] = 0;
+  }
+  for (uint32_t v = 0; v < n; ++v)
+    for (int32_t k = 0; k < S.stay[v] + S.newc[v]; ++k) {
+      leaf_out[S.off[v] + k] = (int32_t)v;
+      expand_out[S.off[v] + k] = k >= S.stay[v];
+    }
+}
+
 }  // namespace tree_host

@@ -94,6 +94,10 @@ def load_library(path=LIB_PATH):
                            ("shipsim_tree_expand", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P, P, C.c_int64,
                                                     P, P]),
                            ("shipsim_tree_backup", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P, P, P, P]),
+                           ("shipsim_tree_init_forest", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P]),
+                           ("shipsim_tree_select_forest", [P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P,
+                                                           C.c_int32, C.c_int32, C.c_int32, C.c_double, P, C.c_int64, P,
+                                                           P, P]),
                            ("shipsim_weather_bytes", [C.c_int32]),
                            ("shipsim_weather_store", [P, P, C.c_int64, C.c_int32, P]),
                            ("shipsim_weather_load", [P, P, C.c_int64, C.c_int32, P]),
@@ -132,7 +136,8 @@ EXPORTED_SYMBOLS = ("shipsim_abi_version", "shipsim_build_info", "shipsim_defaul
                     "shipsim_get_stream_grouping", "shipsim_sbmpc_nominal", "shipsim_tree_bytes", "shipsim_tree_layout",
                     "shipsim_tree_workspace_bytes", "shipsim_tree_init", "shipsim_tree_select", "shipsim_tree_expand",
                     "shipsim_tree_backup", "shipsim_weather_bytes", "shipsim_weather_store", "shipsim_weather_load",
-                    "shipsim_weather_fork", "shipsim_tickmath_eval")
+                    "shipsim_weather_fork", "shipsim_tickmath_eval", "shipsim_tree_init_forest",
+                    "shipsim_tree_select_forest")
 
 
 class Snapshot:
@@ -913,14 +918,18 @@ class SearchTree:
     n_children, child (max_nodes, max_children), visits, value_sum (int64, 24 fractional bits), action, flags — and
     the workspace of its calls, sized for n_workers. Node i is cell i of a StateArchive of max_nodes cells. Made with
     the one-node tree in it; every method is asynchronous on the current stream, allocates nothing and can be
-    captured into a graph."""
+    captured into a graph. n_roots = R > 1 makes a forest (shipsim_tree_init_forest): R roots, nodes 0..R-1, in the
+    one pool, each the root of a tree of its own; header[3] is then R, and select takes the workers per root."""
 
-    def __init__(self, max_nodes, max_children, n_workers, device="cuda"):
+    def __init__(self, max_nodes, max_children, n_workers, n_roots=1, device="cuda"):
         L = load_library()
         self.max_nodes, self.max_children, self.n_workers = int(max_nodes), int(max_children), int(n_workers)
+        self.n_roots = int(n_roots)
         self.layout = tree_layout(self.max_nodes, self.max_children)
         if not 1 <= self.n_workers <= TREE_MAX_WORKERS:
             raise ShipSimError(f"tree: n_workers must be in 1..{TREE_MAX_WORKERS}, not {n_workers}")
+        if not 1 <= self.n_roots <= min(self.max_nodes, self.n_workers):
+            raise ShipSimError(f"tree: n_roots must be in 1..min(max_nodes, n_workers), not {n_roots}")
         self.device = dev = torch.device(device)
         if dev.index is None:
             self.device = dev = torch.device(dev.type, torch.cuda.current_device())
@@ -936,6 +945,9 @@ class SearchTree:
         self.leaf = torch.empty(self.n_workers, dtype=torch.int32, device=dev)
         self.expand_flag = torch.empty(self.n_workers, dtype=torch.int32, device=dev)
         self.node = torch.empty(self.n_workers, dtype=torch.int32, device=dev)
+        # the even split of a forest's workers over its roots: W // R + (r < W % R)
+        r = torch.arange(self.n_roots, dtype=torch.int32, device=dev)
+        self.even_workers = self.n_workers // self.n_roots + (r < self.n_workers % self.n_roots).int()
         self.init()
 
     def _call(self, name, *args):
@@ -953,17 +965,40 @@ class SearchTree:
         return t
 
     def init(self):
-        """The one-node tree: the root, node 0 (shipsim_tree_init)."""
-        self._call("shipsim_tree_init")
+        """The one-node tree: the root, node 0 (shipsim_tree_init); for a forest its n_roots roots
+        (shipsim_tree_init_forest)."""
+        if self.n_roots > 1:
+            self._call("shipsim_tree_init_forest", self.n_roots)
+        else:
+            self._call("shipsim_tree_init")
 
-    def select(self, max_depth, widen=(1, 1), c_explore=1.0):
+    def select(self, max_depth, widen=(1, 1), c_explore=1.0, root_workers=None):
         """Where each of the n_workers workers starts this round (shipsim_tree_select): (leaf, expand), int32 tensors
-        owned by the tree — worker w starts from node leaf[w] and creates a child there iff expand[w] == 1."""
+        owned by the tree — worker w starts from node leaf[w] and creates a child there iff expand[w] == 1.
+        root_workers (shipsim_tree_select_forest): n_roots int32, the workers asked for per root, served in root order
+        until the n_workers are used up; where they sum to less, the trailing workers get leaf -1 (expand passes them
+        through, backup skips them). A forest's default is the even split W // R + (r < W % R); a single tree without
+        root_workers takes shipsim_tree_select. Only a contiguous int32 tensor of n_roots entries on the tree's device
+        (or the default) keeps the class's promise of no allocation: it is passed as it is, and the caller keeps it
+        alive and unchanged for as long as a captured graph reads it. Anything else (a list, a host tensor, another
+        dtype) is copied to the device in this call, which allocates and cannot be captured."""
         c = float(c_explore)
         if not (c >= 0.0 and c != float("inf")):
             raise ShipSimError(f"tree select: c_explore must be finite and >= 0, not {c_explore}")
-        self._call("shipsim_tree_select", self.n_workers, int(max_depth), int(widen[0]), int(widen[1]), C.c_double(c),
-                   _ptr(self.workspace), self.workspace.numel(), _ptr(self.leaf), _ptr(self.expand_flag))
+        if root_workers is None and self.n_roots == 1:
+            self._call("shipsim_tree_select", self.n_workers, int(max_depth), int(widen[0]), int(widen[1]), C.c_double(c),
+                       _ptr(self.workspace), self.workspace.numel(), _ptr(self.leaf), _ptr(self.expand_flag))
+            return self.leaf, self.expand_flag
+        if root_workers is None:
+            rw = self.even_workers
+        else:
+            rw = torch.as_tensor(root_workers, dtype=torch.int32, device=self.device).contiguous().reshape(-1)
+            if rw.numel() != self.n_roots:
+                raise ShipSimError(f"tree select: {rw.numel()} entries of root_workers for {self.n_roots} roots")
+        self._call("shipsim_tree_select_forest", self.n_workers, self.n_roots, _ptr(rw), int(max_depth), int(widen[0]),
+                   int(widen[1]), C.c_double(c), _ptr(self.workspace), self.workspace.numel(), _ptr(self.leaf),
+                   _ptr(self.expand_flag))
+        self._keep_roots = rw  # (the call is asynchronous: a copy made above must outlive it)
         return self.leaf, self.expand_flag
 
     def expand(self, action, leaf=None, expand=None):
@@ -993,9 +1028,9 @@ class SearchTree:
         return int(self.header[0].item())
 
 
-def tree_select(tree, max_depth, widen=(1, 1), c_explore=1.0):
+def tree_select(tree, max_depth, widen=(1, 1), c_explore=1.0, root_workers=None):
     """SearchTree.select as a function: (leaf, expand)."""
-    return tree.select(max_depth, widen, c_explore)
+    return tree.select(max_depth, widen, c_explore, root_workers)
 
 
 def tree_expand(tree, action, leaf=None, expand=None):

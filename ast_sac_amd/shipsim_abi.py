@@ -106,6 +106,7 @@ TREE_MAX_CHILDREN = 64  # SHIPSIM_TREE_MAX_CHILDREN: the most children of a sear
 TREE_MAX_DEPTH = 32  # SHIPSIM_TREE_MAX_DEPTH
 TREE_MAX_WORKERS = 1 << 22  # SHIPSIM_TREE_MAX_WORKERS: the most workers of one select / expand / backup
 TREE_SCAN_TILE = 1024  # SHIPSIM_TREE_SCAN_TILE
+TREE_HDR_ROOTS = 3  # the tree header's fourth int: n_roots of a forest (shipsim_tree_init_forest / _select_forest); 0 reads as 1
 
 
 def events_to_string(bits):

@@ -461,7 +461,8 @@ int shipsim_archive_elect(int32_t n_envs, int32_t n_cells, const int32_t* cell, 
  * buffer, 16-byte aligned, of shipsim_tree_bytes(max_nodes, max_children) bytes: max_nodes in
  * 1..SHIPSIM_ARCHIVE_MAX_CELLS, max_children (C) in 1..SHIPSIM_TREE_MAX_CHILDREN. It is a structure of arrays whose
  * byte offsets shipsim_tree_layout writes into offsets_out[SHIPSIM_TREE_LAYOUT_FIELDS], in this order:
- *   header      int32[4]: n_nodes; dropped, the new nodes the pool had no room for; skipped, the backups not taken; 0
+ *   header      int32[4]: n_nodes; dropped, the new nodes the pool had no room for; skipped, the backups not taken;
+ *               hdr[3] = n_roots, the roots of a forest (0, as shipsim_tree_init writes it, reads as 1)
  *   parent      int32 [max_nodes], -1 for the root        depth      int32 [max_nodes]
  *   n_children  int32 [max_nodes]                         child      int32 [max_nodes * C], in creation order
  *   visits      int32 [max_nodes]                         value_sum  int64 [max_nodes], round(value * 2^24) summed
@@ -502,7 +503,30 @@ int shipsim_archive_elect(int32_t n_envs, int32_t n_cells, const int32_t* cell, 
  *
  * SHIPSIM_EINVAL, before any device call: a NULL tree, workspace or required array; sizes out of range;
  * tree_bytes != shipsim_tree_bytes(...); a tree or workspace not 16-byte aligned; a workspace too small; c_explore
- * negative or not finite. The arithmetic is ast_sac_amd/csrc/shipsim_tree_host.hpp, restated in tests/tree_ref.py. */
+ * negative or not finite. The arithmetic is ast_sac_amd/csrc/shipsim_tree_host.hpp, restated in tests/tree_ref.py.
+ *
+ * A forest is R = n_roots roots in one node pool, sharing one archive and one round of calls: nodes 0..R-1, each with
+ * parent -1, depth 0, action 0 and no children. Everything under a root is a tree as above: R trees of one problem
+ * (root-parallel search), or one tree per weather when root r is the reset state of env r under env r's weather.
+ *
+ * shipsim_tree_init_forest writes n_nodes = n_roots, hdr[3] = n_roots, zero counters and the R roots
+ * (1 <= n_roots <= max_nodes).
+ *
+ * shipsim_tree_select_forest is shipsim_tree_select with the R roots, not node 0, as where the workers start.
+ * root_workers is a device array of n_roots int32, the workers asked for per root; the roots are served in id order
+ * until the W workers are used up: root r receives
+ *     a_r = min(max(c_r, 0), W - min(W, sum over r' < r of max(c_r', 0)))
+ * arrivals (the sum formed with adds that saturate at W, so the result is defined whatever the array holds) and routes
+ * them exactly as the root of a tree routes its W. It serves min(n_roots, the header's roots, n_nodes) roots. The
+ * output order is select's: by increasing node id, a node's staying workers before its widening ones. When the a_r sum
+ * to less than W, the trailing workers get leaf_out[w] = -1 and expand_out[w] = 0: shipsim_tree_expand passes them
+ * through (node_out[w] = -1) and shipsim_tree_backup counts them as skipped. With n_roots = 1 and root_workers = {W} it
+ * returns what shipsim_tree_select returns. Refused with SHIPSIM_EINVAL, beside everything shipsim_tree_select
+ * refuses: n_roots < 1, n_roots > max_nodes, n_roots > n_workers (level 0 holds a root per worker at the most), a NULL
+ * root_workers.
+ *
+ * shipsim_tree_expand and shipsim_tree_backup serve a forest as they are: expand does not know roots, and backup
+ * walks up to the node whose parent is -1. */
 #define SHIPSIM_TREE_MAX_CHILDREN 64
 #define SHIPSIM_TREE_MAX_DEPTH 32
 #define SHIPSIM_TREE_MAX_WORKERS (1 << 22)
@@ -520,6 +544,12 @@ int shipsim_tree_expand(void* tree, int64_t tree_bytes, int32_t max_nodes, int32
                         int64_t workspace_bytes, int32_t* node_out, void* stream);
 int shipsim_tree_backup(void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children, int32_t n_workers,
                         const int32_t* node, const double* value, const uint8_t* terminal, void* stream);
+int shipsim_tree_init_forest(void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children, int32_t n_roots,
+                             void* stream);
+int shipsim_tree_select_forest(const void* tree, int64_t tree_bytes, int32_t max_nodes, int32_t max_children,
+                               int32_t n_workers, int32_t n_roots, const int32_t* root_workers, int32_t max_depth,
+                               int32_t wnum, int32_t wden, double c_explore, void* workspace, int64_t workspace_bytes,
+                               int32_t* leaf_out, int32_t* expand_out, void* stream);
 
 /* ---- trajectory recording (f1: simulation_results export) ----------------------------------
  * Per-tick rows of ShipModelAST/SimpleShipModel.store_simulation_data (ship_model.py:903-957,

@@ -8,7 +8,17 @@ most-visited action sequence. A worker that stays at a terminal leaf takes no de
 illustration, not an estimator: whether the tree finds more collisions than random search is reported, not asserted.
 Writes profiles/tree_search_example.json.
 
-    python scripts/tree_search.py [--out FILE] [--envs N] [--rounds R] [--max-nodes M] [--children C]
+--roots R searches a forest: R trees in the one node pool, the envs split evenly over their roots, every root the
+reset state (root-parallel search). With a weather range flag, env i draws a weather of its own (weather.py:
+sample_weather, seed --weather_seed) and root r is the reset state of env r under env r's weather: one tree per
+weather, which needs --roots >= 2 (one tree stands for one weather); the envs beyond the roots draw weathers too, but
+sail under the weather of the node they play from their first load on. Reported per root then: its visits and its
+most-visited action sequence (visits_per_root, best_path_deg_per_root; root_visits and best_path_deg stay root 0's).
+The random leg sails under the same drawn weathers.
+
+    python scripts/tree_search.py [--out FILE] [--envs N] [--rounds R] [--max-nodes M] [--children C] [--roots R]
+        [--wind_speed_range LO HI] [--wind_direction_range LO HI] [--current_speed_range LO HI]
+        [--current_direction_range LO HI] [--weather_seed S]
 """
 import argparse
 import json
@@ -24,6 +34,12 @@ sys.path.insert(0, ROOT)
 from ast_sac_amd import shipsim_abi as abi  # noqa: E402
 from ast_sac_amd.rl_env.ship_in_transit.env import BatchedMultiShipRLEnv, default_args  # noqa: E402
 from ast_sac_amd.rl_env.ship_in_transit.tree_search import TreeSearch  # noqa: E402
+from ast_sac_amd.rl_env.ship_in_transit.weather import sample_weather  # noqa: E402
+
+# the runner's four range flags -> sample_weather's keyword arguments
+WEATHER_RANGE_FLAGS = (("wind_speed_range", "wind_speed", "m/s"), ("wind_direction_range", "wind_direction_deg", "degrees"),
+                       ("current_speed_range", "current_speed", "m/s"),
+                       ("current_direction_range", "current_direction_deg", "degrees"))
 
 LIMIT = float(np.deg2rad(30))
 
@@ -33,9 +49,9 @@ def uniform_policy(n, dev, seed):
     return lambda obs: (torch.rand(n, generator=g, device=dev, dtype=torch.float32) * 2.0 - 1.0) * LIMIT
 
 
-def tree_leg(dev, n, rounds, max_nodes, children, widen, c_explore, seed):
-    env = BatchedMultiShipRLEnv(default_args(collav_mode="sbmpc"), n, device=dev)
-    ts = TreeSearch(env, max_nodes, max_children=children, widen=widen, c_explore=c_explore)
+def tree_leg(dev, n, rounds, max_nodes, children, widen, c_explore, seed, roots=1, weather=None):
+    env = BatchedMultiShipRLEnv(default_args(collav_mode="sbmpc"), n, device=dev, weather=weather)
+    ts = TreeSearch(env, max_nodes, max_children=children, widen=widen, c_explore=c_explore, n_roots=roots)
     policy = uniform_policy(n, dev, seed)
     episodes = torch.zeros((), dtype=torch.int64, device=dev)
     collisions, ticks = torch.zeros_like(episodes), torch.zeros_like(episodes)
@@ -56,12 +72,16 @@ def tree_leg(dev, n, rounds, max_nodes, children, widen, c_explore, seed):
                depth=int(t.depth[:nn].max()), terminal_nodes=int((t.flags[:nn] & 1).sum()),
                root_visits=int(t.visits[0]), best_path_deg=[float(np.rad2deg(a)) for a in actions],
                best_path_visits=[int(t.visits[v]) for v in nodes], seconds=dt)
+    if roots > 1:
+        res["roots"] = roots
+        res["visits_per_root"] = t.visits[:roots].cpu().tolist()
+        res["best_path_deg_per_root"] = [[float(np.rad2deg(a)) for a in ts.best_path(root=r)[0]] for r in range(min(roots, 16))]
     env.close()
     return res
 
 
-def random_leg(dev, n, tick_budget, seed):
-    env = BatchedMultiShipRLEnv(default_args(collav_mode="sbmpc"), n, device=dev)
+def random_leg(dev, n, tick_budget, seed, weather=None):
+    env = BatchedMultiShipRLEnv(default_args(collav_mode="sbmpc"), n, device=dev, weather=weather)
     policy = uniform_policy(n, dev, seed)
     n_dec = int(env.cfg.max_sampling_frequency)
     episodes = collisions = ticks = 0
@@ -96,14 +116,26 @@ def main():
     ap.add_argument("--widen", type=int, nargs=2, default=(4, 1))
     ap.add_argument("--c-explore", type=float, default=50.0)
     ap.add_argument("--seed", type=int, default=20261021)
+    ap.add_argument("--roots", type=int, default=1, metavar="R", help="search a forest of R trees (envs 0..R-1 are the roots)")
+    for flag, _, unit in WEATHER_RANGE_FLAGS:
+        ap.add_argument("--" + flag, type=float, nargs=2, default=None, metavar=("LO", "HI"), help=f"per-env draw, {unit}")
+    ap.add_argument("--weather_seed", type=int, default=0, metavar="S", help="env i draws its weather from PCG64(S + i)")
     args = ap.parse_args()
+    ranges = {kw: tuple(getattr(args, flag)) for flag, kw, _ in WEATHER_RANGE_FLAGS if getattr(args, flag) is not None}
+    if not 1 <= args.roots <= args.envs:
+        ap.error("--roots must be in 1..--envs")
+    if ranges and args.roots < 2:
+        ap.error("a weather range needs --roots >= 2: one tree stands for one weather")
     if not torch.cuda.is_available():
         raise SystemExit("tree_search.py needs a HIP device")
     dev = torch.device("cuda", 0)
-    tree = tree_leg(dev, args.envs, args.rounds, args.max_nodes, args.children, tuple(args.widen), args.c_explore, args.seed)
-    rand = random_leg(dev, args.envs, tree["env_ticks"], args.seed + 1)
+    weather = sample_weather(args.envs, seed=args.weather_seed, **ranges) if ranges else None
+    tree = tree_leg(dev, args.envs, args.rounds, args.max_nodes, args.children, tuple(args.widen), args.c_explore, args.seed,
+                    roots=args.roots, weather=weather)
+    rand = random_leg(dev, args.envs, tree["env_ticks"], args.seed + 1, weather=weather)
     res = dict(envs=args.envs, collav="sbmpc", obstacle_ships=1, max_children=args.children, widen=list(args.widen),
-               c_explore=args.c_explore, device=torch.cuda.get_device_name(dev),
+               c_explore=args.c_explore, device=torch.cuda.get_device_name(dev), roots=args.roots,
+               **({} if weather is None else dict(weather=dict(seed=args.weather_seed, ranges={k: list(v) for k, v in ranges.items()}))),
                note="collision counts of one seeded run each: an illustration, not an estimate of a probability",
                tree_search=tree, uniform_random=rand)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
